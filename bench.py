@@ -13,6 +13,12 @@ step still traces its own light pass, builds its own sampler and renders its own
   python bench.py [--gpus N] [--steps K] [--warmup W]      N > 1 started the plain way: this process only spawns the N ranks
                                                             (python -m torch.distributed.run ... as a child, before any GPU call) and relays rank 0's line
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run only sets up, warms up (W steps, rounded up to whole launches of the timed size), times the K steps and prints the
+headline line. --full adds everything else the benchmark measures: the event-counting and isolated-kernel passes (roofline,
+kernels_ms, events_per_eye_path), the long steady-state run, the reference's loop form and the viewer loop, the CPU baseline and
+the fast-math line. --dump-outputs DIR writes the film the timed steps accumulated (what spcbpt_read_accum hands a caller) as
+DIR/film_accum.npy, for comparing two builds on the same inputs.
 """
 from __future__ import annotations
 
@@ -32,6 +38,7 @@ import numpy as np  # noqa: E402
 import __graft_entry__ as entry  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
 
 
 def make_scene(pkg, name, tris):
@@ -179,7 +186,7 @@ def fast_math_line(pkg, args):
     reciprocal / square root like the reference's own --use_fast_math build; image-level bars of its own, tests/test_gpu_fast_build.py),
     in a child interpreter (two libraries with the same exports cannot share a process), after this process's measurements are done."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline",
            "--fast-math-line", "0", "--sync-each-frames", "0", "--long-steps", "0", "--scene", args.scene, "--tris", str(args.tris),
            "--width", str(args.width), "--height", str(args.height), "--light-paths", str(args.light_paths), "--tuple", args.tuple]
     env = dict(os.environ, SPCBPT_LIB=pkg.api.FAST_LIB_PATH)
@@ -195,6 +202,20 @@ def fast_math_line(pkg, args):
         return {"error": f"{type(e).__name__}: {e}"[:300]}
 
 
+def dump_outputs(out_dir, film, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the accumulation film as out_dir/film_accum.npy (float32, h x w x 4).  A film beyond `limit` bytes is written
+    as a fixed, seeded sample of its pixels (n x 4) with their flat pixel indices in film_accum_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes + 4096 > limit:
+        px = film.reshape(-1, film.shape[-1])
+        n = (limit - 4096) // (px.shape[1] * 4 + 8)     # every kept pixel also costs its index
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+        np.save(os.path.join(out_dir, "film_accum_index.npy"), idx.astype(np.float64))
+        film = px[idx]
+    np.save(os.path.join(out_dir, "film_accum.npy"), film)
+
+
 def frames_per_launch(steps: int, max_batch: int = 32) -> int:
     """Frames per eye / light launch for a run of `steps` steps: as few launches as `max_batch` allows, all of (nearly) the same size."""
     launches = max(1, -(-steps // max_batch))
@@ -204,8 +225,13 @@ def frames_per_launch(steps: int, max_batch: int = 32) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="GPUs of this node (default: WORLD_SIZE when launched by torch.distributed.run, else 1)")
-    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=32, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: roofline / kernel-time / event-count passes, the long run "
+                         "(--long-steps), the reference's loop form and the viewer loop (--sync-each-frames), the CPU baseline and the fast-math line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the film they accumulated as DIR/film_accum.npy (float32)")
     ap.add_argument("--scene", default="bedroom")
     ap.add_argument("--tris", type=int, default=1_000_000)
     ap.add_argument("--width", type=int, default=1920)
@@ -217,11 +243,11 @@ def main():
                          "minimal: single-leaf trees, Gamma rows = Q (the cheapest valid tuple, no classification work)")
     ap.add_argument("--scene-route", default="gltf", choices=["gltf", "memory"],
                     help="gltf: write the generated scene as glTF 2.0 and read it back with the C++ reader (default); memory: hand the arrays over directly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--long-steps", type=int, default=256, help="steps of the extra steady-state run reported as ms_per_step_long (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--long-steps", type=int, default=256, help="with --full: steps of the extra steady-state run reported as ms_per_step_long (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = the CPUs this process can really use: host_cpus())")
-    ap.add_argument("--fast-math-line", type=int, default=1, help="1 (default, one GPU): report the same run on the opt-in approximate-arithmetic library as a second line (fast_math_build)")
-    ap.add_argument("--sync-each-frames", type=int, default=16, help="frames of the extra pass in the reference's loop form -- one light pass, one build, one eye "
+    ap.add_argument("--fast-math-line", type=int, default=1, help="with --full, 1 (default, one GPU): report the same run on the opt-in approximate-arithmetic library as a second line (fast_math_build)")
+    ap.add_argument("--sync-each-frames", type=int, default=16, help="with --full: frames of the extra pass in the reference's loop form -- one light pass, one build, one eye "
                     "launch and a device sync per frame (optixPathTracer.cpp:791-822) -- reported as ms_per_frame_sync_each (0 = skip)")
     ap.add_argument("--cpu-band-stride", type=int, default=0, help="0 = choose from the host core count (about 10-30 s of CPU work)")
     ap.add_argument("--render-streams", type=int, default=0,
@@ -255,6 +281,8 @@ def main():
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if gpus_given and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
         # a launcher (or an outer harness that exported WORLD_SIZE) disagrees with the request: running on WORLD_SIZE GPUs and
         # labelling the line --gpus would be a wrong number, and so would the reverse
@@ -486,60 +514,65 @@ def main():
         torch.cuda.synchronize()
 
     r.clear_accum()
-    state["phase_left"] = args.warmup
-    for f in range(args.warmup):
+    # the warm-up runs whole launches of the timed size: the first launch of n frames allocates the per-frame result films of
+    # spcbpt_launch_eye_batch up to n (33 MB each at 1920x1080), which must not happen inside the timed steps (--full: the
+    # isolated-kernel pass below runs such launches before them)
+    n_warm = args.warmup if args.full else -(-args.warmup // batch) * batch
+    state["phase_left"] = n_warm
+    for f in range(n_warm):
         step(f)
     flush()
-    # event counts of ONE launch of the dominant kernel -> algorithmic bytes per launch (untimed)
-    r.sync()
-    if not ahead:
-        r.launch("light trace", 999)
-    else:
-        r.launch("light trace", state["next_light"]); state["next_light"] += 1
-    if ex is not None:
-        ex.allgather_lvc()
-    elif comm is not None:
-        comm.exchange_lvc()
-    r.build_sampler()
-    # ... counted twice: (1) in the REFERENCE's order (two relabels per connection, one per RMIS update, a bisection per first
-    # stage: the contract's table of SURVEY 8(d), kept as roofline.contract_reference_order), and (2) by the instantiation the
-    # timed runs use (labels cached per vertex, guided resampling, Gamma / Q from its table): the events that EXECUTE -- roofline.frac is computed from (2)
-    r.enable_counters(1)
-    r.reset_counters()
-    r.launch("SPCBPT_eye", 999, rows)
-    r.sync()
-    c_ref = r.counters()
-    r.enable_counters(2)
-    r.reset_counters()
-    r.launch("SPCBPT_eye", 999, rows)
-    r.sync()
-    c_eye = r.counters()
-    ph = r.phase_clocks()
-    r.enable_counters(False)
-    bytes_per_launch = pkg.algorithmic_bytes(c_eye)
-    bytes_ref_per_launch = pkg.algorithmic_bytes(c_ref)
-    bytes_actual_per_launch = pkg.algorithmic_bytes(c_eye, pkg.api.BYTES_ACTUAL)
-    lane_util = {"node_step": round(ph["node_lanes"] / max(ph["node_slots"], 1), 4), "triangle_step": round(ph["tri_lanes"] / max(ph["tri_slots"], 1), 4)}
+    if args.full:   # the passes behind roofline / kernels_ms / events_per_eye_path (untimed)
+        # event counts of ONE launch of the dominant kernel -> algorithmic bytes per launch (untimed)
+        r.sync()
+        if not ahead:
+            r.launch("light trace", 999)
+        else:
+            r.launch("light trace", state["next_light"]); state["next_light"] += 1
+        if ex is not None:
+            ex.allgather_lvc()
+        elif comm is not None:
+            comm.exchange_lvc()
+        r.build_sampler()
+        # ... counted twice: (1) in the REFERENCE's order (two relabels per connection, one per RMIS update, a bisection per first
+        # stage: the contract's table of SURVEY 8(d), kept as roofline.contract_reference_order), and (2) by the instantiation the
+        # timed runs use (labels cached per vertex, guided resampling, Gamma / Q from its table): the events that EXECUTE -- roofline.frac is computed from (2)
+        r.enable_counters(1)
+        r.reset_counters()
+        r.launch("SPCBPT_eye", 999, rows)
+        r.sync()
+        c_ref = r.counters()
+        r.enable_counters(2)
+        r.reset_counters()
+        r.launch("SPCBPT_eye", 999, rows)
+        r.sync()
+        c_eye = r.counters()
+        ph = r.phase_clocks()
+        r.enable_counters(False)
+        bytes_per_launch = pkg.algorithmic_bytes(c_eye)
+        bytes_ref_per_launch = pkg.algorithmic_bytes(c_ref)
+        bytes_actual_per_launch = pkg.algorithmic_bytes(c_eye, pkg.api.BYTES_ACTUAL)
+        lane_util = {"node_step": round(ph["node_lanes"] / max(ph["node_slots"], 1), 4), "triangle_step": round(ph["tri_lanes"] / max(ph["tri_slots"], 1), 4)}
 
-    # duration of the dominant kernel by itself (roofline): a few frames with a sync after each, so that no neighbouring
-    # frame's kernel shares the GPU with it; HIP events on the kernel's own stream (spcbpt_kernel_time)
-    r.enable_kernel_timing(True)
-    r.reset_kernel_time()
-    n_iso = 8 if batch == 1 else 2 * batch   # whole launches only: every timed launch holds `batch` frames
-    state["phase_left"] = n_iso
-    for f in range(n_iso):
-        step(1000 + f, isolate=True)
-        if batch == 1 or not queued:      # batched: a sync after each launch = after every `batch` steps
-            r.sync()
-    flush()
-    r.sync()
-    k_ms, k_n = r.kernel_time("spcbpt_render")
-    bytes_per_launch *= batch             # a batched launch renders `batch` frames (the last one of this pass may hold fewer)
-    bytes_ref_per_launch *= batch
-    bytes_actual_per_launch *= batch
-    lt_ms, _ = r.kernel_time("light_trace")
-    sb_ms, _ = r.kernel_time("sampler_build")
-    cp_ms, _ = r.kernel_time("lvc_compact")
+        # duration of the dominant kernel by itself (roofline): a few frames with a sync after each, so that no neighbouring
+        # frame's kernel shares the GPU with it; HIP events on the kernel's own stream (spcbpt_kernel_time)
+        r.enable_kernel_timing(True)
+        r.reset_kernel_time()
+        n_iso = 8 if batch == 1 else 2 * batch   # whole launches only: every timed launch holds `batch` frames
+        state["phase_left"] = n_iso
+        for f in range(n_iso):
+            step(1000 + f, isolate=True)
+            if batch == 1 or not queued:      # batched: a sync after each launch = after every `batch` steps
+                r.sync()
+        flush()
+        r.sync()
+        k_ms, k_n = r.kernel_time("spcbpt_render")
+        bytes_per_launch *= batch             # a batched launch renders `batch` frames (the last one of this pass may hold fewer)
+        bytes_ref_per_launch *= batch
+        bytes_actual_per_launch *= batch
+        lt_ms, _ = r.kernel_time("light_trace")
+        sb_ms, _ = r.kernel_time("sampler_build")
+        cp_ms, _ = r.kernel_time("lvc_compact")
 
     r.clear_accum()
     r.reset_kernel_time()
@@ -560,12 +593,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    k_ms_overlapped, _ = r.kernel_time("spcbpt_render")   # span of the same kernel while frames overlap (timed region)
-    r.enable_kernel_timing(False)
+    if args.full:
+        k_ms_overlapped, _ = r.kernel_time("spcbpt_render")   # span of the same kernel while frames overlap (timed region)
+        r.enable_kernel_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r.read_accum())
 
     # ---- beside the contract's K steps: a long steady-state run of the same loop, and the reference's own loop form
     ms_long = None
-    if args.long_steps > 0:
+    if args.full and args.long_steps > 0:
         nl = -(-args.long_steps // batch) * batch      # whole launches
         barrier()
         t1 = time.perf_counter()
@@ -583,7 +619,7 @@ def main():
     ms_sync_each_ahead = None
     ms_viewer = None
     ms_viewer_moving = None
-    if args.sync_each_frames > 0 and ex is None:
+    if args.full and args.sync_each_frames > 0 and ex is None:
         # optixPathTracer.cpp:791-822: launchLVCTrace (light pass + LVC_Process) then launchSubframe, a device sync after each
         # (513, 634) -- one frame in flight, nothing batched, nothing ahead
         r.sync()
@@ -655,13 +691,26 @@ def main():
     eye_paths = args.width * args.height
     total_paths = (eye_paths + M) * args.steps
     value = total_paths / dt / 1e6
-    achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
 
     if args.write_image and rank == 0:
         img = r.read_accum()
         np.save(args.write_image, img)
 
     if rank == 0:
+        out = {
+            "metric": "Mpaths/sec (whole node), SPCBPT, 1920x1080",
+            "value": round(value, 3), "unit": "Mpaths/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.scene} scene{' read from glTF' if args.scene_route == 'gltf' else ''} ({info['n_triangles']} triangles, SAH BVH of {info['n_bvh_nodes']} quantised 4-wide nodes, depth "
+                                   f"{info['bvh_depth']}), {args.width}x{args.height}, SPCBPT: {M} light paths + "
+                                   f"{eye_paths} eye paths per subframe, CONNECTION_N=3, subspace tuple: {args.tuple}, light pass geometry "
+                                   f"{ncore} cores x {mpc} paths x {pad} slots ({args.light_geometry})",
+                       "preprocess_s": round(t_pre, 2), "warmup_steps_run": n_warm, "frames_in_flight": streams * batch, "frames_per_eye_launch": batch, "light_passes_ahead": (batch if lbatch else depth) if ahead else 0, "light_passes_per_launch": batch if lbatch else 1, "sampler_builds_ahead": batch if build_ahead else 0, "parallelism": "1 GPU" if world == 1 and comm is None else f"{world} GPUs: interleaved 8-row bands, LVC all-gather + film band gather over RCCL ({'C++ host libspcbpt_mgpu: ' + comm_transport + ' transport, ' + str(comm_world) + ' ranks seen by the communicator' if comm is not None else 'torch.distributed harness (--exchange python)'}" + (f", shard capacity {comm.shard_capacity} vertices, {'one exchange per light batch' if xbatch else 'one exchange per frame'}" if comm is not None else "") + ")",
+                       "host": "single context" if dist is None else ("libspcbpt_mgpu" if comm is not None else "torch.distributed harness"), "rccl_ranks": comm_world if comm is not None else (world if dist is not None else 0)},
+        }
+    if rank == 0 and args.full:
+        achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
         # HBM-side traffic comes from rocprofv3 PMC passes (tools/profile_round.sh -> tools/pmc_summary.py), which cannot run inside
         # this process; the committed summary is quoted only if it profiled THIS code (hash of csrc/) in THIS launch form
         traffic = traffic_low = valu_issue = None
@@ -701,10 +750,7 @@ def main():
         # (the executed order reads 32 CMF values per first stage where the bisection probes 10, and 1 tree descent per vertex where
         # the reference re-descends per connection: neither order is the lesser on every event)
         bytes_min_per_launch = pkg.algorithmic_bytes({k: min(c_eye[k], c_ref[k]) for k in c_eye}) * batch
-        out = {
-            "metric": "Mpaths/sec (whole node), SPCBPT, 1920x1080",
-            "value": round(value, 3), "unit": "Mpaths/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
+        out.update({
             "ms_per_step_long": None if ms_long is None else round(ms_long, 3),
             "ms_per_frame_sync_each": None if ms_sync_each is None else round(ms_sync_each, 3),
             "ms_per_frame_sync_each_light_ahead": None if ms_sync_each_ahead is None else round(ms_sync_each_ahead, 3),
@@ -714,13 +760,6 @@ def main():
                       "ms_per_frame_sync_each": "the reference's loop form (optixPathTracer.cpp:791-822): one light pass, one sampler build, one eye launch and a device sync per frame",
                       "ms_per_frame_viewer": "spcbpt_viewer_frame in its default mode: one complete, displayable frame per call (the same frames as the reference's loop), the next frame traced while this one is shown",
                       "ms_per_frame_viewer_moving": "the same loop while the camera is dragged (an event before every call: each frame is subframe 0 of a new view; nothing is traced ahead to be dropped)"},
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.scene} scene{' read from glTF' if args.scene_route == 'gltf' else ''} ({info['n_triangles']} triangles, SAH BVH of {info['n_bvh_nodes']} quantised 4-wide nodes, depth "
-                                   f"{info['bvh_depth']}), {args.width}x{args.height}, SPCBPT: {M} light paths + "
-                                   f"{eye_paths} eye paths per subframe, CONNECTION_N=3, subspace tuple: {args.tuple}, light pass geometry "
-                                   f"{ncore} cores x {mpc} paths x {pad} slots ({args.light_geometry})",
-                       "preprocess_s": round(t_pre, 2), "frames_in_flight": streams * batch, "frames_per_eye_launch": batch, "light_passes_ahead": (batch if lbatch else depth) if ahead else 0, "light_passes_per_launch": batch if lbatch else 1, "sampler_builds_ahead": batch if build_ahead else 0, "parallelism": "1 GPU" if world == 1 and comm is None else f"{world} GPUs: interleaved 8-row bands, LVC all-gather + film band gather over RCCL ({'C++ host libspcbpt_mgpu: ' + comm_transport + ' transport, ' + str(comm_world) + ' ranks seen by the communicator' if comm is not None else 'torch.distributed harness (--exchange python)'}" + (f", shard capacity {comm.shard_capacity} vertices, {'one exchange per light batch' if xbatch else 'one exchange per frame'}" if comm is not None else "") + ")",
-                       "host": "single context" if dist is None else ("libspcbpt_mgpu" if comm is not None else "torch.distributed harness"), "rccl_ranks": comm_world if comm is not None else (world if dist is not None else 0)},
             # `bound` names the contract's roofline (north_star: the HBM-read roofline; the path has no MFMA work); what really limits the
             # kernel is in `limiter` -- no unit is saturated, the waves' issue slots and their waits for gathers are
             "roofline": {"bound": "hbm", "limiter": "latency / VALU issue of partly filled waves (no unit saturated)" if nearest else None,
@@ -758,7 +797,7 @@ def main():
             "events_per_eye_path": {k: round(v / max(c_eye["eye_paths"], 1), 3) for k, v in c_eye.items()
                                     if k in ("closest_rays", "shadow_rays", "node_visits", "tri_tests", "surface_vertices",
                                              "connections", "tree_nodes", "cmf_probes", "gamma_q_reads")},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pkg, scene, args, tup)
         if args.fast_math_line and world == 1 and comm is None and ex is None and not os.environ.get("SPCBPT_LIB") and os.path.exists(pkg.api.FAST_LIB_PATH):

@@ -45,3 +45,23 @@ def test_cpu_baseline_runs_on_the_cpus_the_box_grants(tmp_path):
     (v1 / "cpu" / "cpu.cfs_quota_us").write_text("-1\n")           # v1: no quota
     assert b.host_cpus(str(v1)) == min(n, len(os.sched_getaffinity(0)))
     assert b.host_cpus(str(tmp_path / "nothing")) == min(n, len(os.sched_getaffinity(0)))
+
+
+def test_dumped_outputs_are_float32_and_capped(tmp_path):
+    """--dump-outputs: the film as it is when it fits; a larger one as the same seeded pixel sample every time, within the cap."""
+    import numpy as np
+    b = _bench()
+    film = np.random.default_rng(1).random((40, 60, 4)).astype(np.float32)
+    b.dump_outputs(str(tmp_path / "whole"), film)
+    got = np.load(tmp_path / "whole" / "film_accum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    assert not (tmp_path / "whole" / "film_accum_index.npy").exists()
+    limit = 20_000                                                  # 38 400 B of film: sampled
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), film, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    s, i = np.load(tmp_path / "a" / "film_accum.npy"), np.load(tmp_path / "a" / "film_accum_index.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == (i.size, 4) and i.size > 0
+    assert np.array_equal(s, film.reshape(-1, 4)[i.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / "b" / "film_accum.npy"))
+    assert np.array_equal(i, np.load(tmp_path / "b" / "film_accum_index.npy"))

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/stats_$TAG; rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --fast-math-line 0 > $OUT/bench.json 2> $OUT/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --fast-math-line 0 > $OUT/bench.json 2> $OUT/log.txt
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)
 cp "$f" $R/gpurun_out/${TAG}_driver_cmd_kernel_stats.csv
 find $OUT -name "*kernel_trace.csv" -delete
