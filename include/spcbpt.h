@@ -311,12 +311,29 @@ int spcbpt_image_size(spcbpt_ctx* ctx, int* width, int* height);
  * height RGBA floats as the .hdr file stores them (row 0 = top; spcbpt_hdr_load); the context keeps the row-flipped texture
  * HDRLoader::loadTexture makes and the sampling CMF envMapCMFBuild makes.  Light sub-paths then start on the sky with probability
  * 1 / n_lights (cuProg.h:611-666), "SPCBPT_eye" connects to sky vertices (raygen.cu:234-258, rmis.h:249-280) and "pt" samples the
- * sky by next-event estimation and shows it to primary rays (hit_program.cu:502-518, raygen.cu:687-697); an eye SUB-PATH that
- * leaves the scene never sees it.  center / radius = sky.center / sky.r (upstream: centre and diagonal of the scene
+ * sky by next-event estimation and shows it to primary rays (hit_program.cu:502-518, raygen.cu:687-697).  As upstream, an eye
+ * SUB-PATH that leaves the scene sees nothing by default: spcbpt_set_environment_mode below opts in.  center / radius = sky.center / sky.r (upstream: centre and diagonal of the scene
  * box it computes); radius <= 0 or center == NULL: centre and diagonal of the true bounding box.  The quad lights'
  * patch subspaces move up by 100 (their div_level^2 may sum to 100 at most).  Call once, before the first light pass. */
 int spcbpt_set_environment(spcbpt_ctx* ctx, const float* rgba, int width, int height, const float* center, float radius);
 int spcbpt_get_environment(spcbpt_ctx* ctx, int* width, int* height, float center[3], float* radius, int* n_lights);
+/* Opt-in corrections of the sky's strategies (default 0 = upstream's behaviour); flags take effect only while the context has an
+ * environment map, so a sky-less context renders bit-identically whatever they are.  May be called before or after
+ * spcbpt_set_environment.
+ *   SPCBPT_ENV_EYE_SEES_SKY              an eye sub-path of "SPCBPT_eye" that leaves the scene sees the sky: the strategy
+ *                                        rmis::light_hit_env (rmis.h:325-358) weights, which upstream never calls although the
+ *                                        weights of the other sky strategies count it -- without it the image is biased dark
+ *                                         and directly seen sky is black.  The flux multiplier of the eye vertex is
+ *                                        taken towards the sky (upstream's copy has the sign of the emitter case, HISTORY q1).
+ *                                        Event-counting eye launches (spcbpt_enable_counters, or classifier trees with direction
+ *                                        nodes) then return SPCBPT_ERR_STATE: their kernels do not evaluate the strategy.
+ *   SPCBPT_ENV_PT_SKY_SHADOW_ALONG_DIR   the shadow ray of "pt"'s sky sample ends at P + d 2r instead of upstream's P + d + 2r
+ *                                        (the scalar added to every component, q18).
+ * Unknown bits: SPCBPT_ERR_INVALID_ARG; a deferred frame outstanding: SPCBPT_ERR_STATE.  Waits for the context's streams; the
+ * film is not touched. */
+enum { SPCBPT_ENV_EYE_SEES_SKY = 1, SPCBPT_ENV_PT_SKY_SHADOW_ALONG_DIR = 2 };
+int spcbpt_set_environment_mode(spcbpt_ctx* ctx, int flags);
+int spcbpt_get_environment_mode(spcbpt_ctx* ctx, int* flags);
 /* Radiance .hdr reader = HDRLoader (scene_shift.cpp:334-500): RGBE, flat or new-style RLE scanlines, "-Y h +X w" only.  rgba == NULL:
  * size query.  The fourth float of a texel is 0 (upstream leaves it unset). */
 int spcbpt_hdr_load(const char* path, int* width, int* height, float* rgba, size_t capacity_floats);
@@ -397,6 +414,9 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *   SPCBPT_UNIT_EYE_STEP in 36: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf seed ray direction3 flags(bit 0: d11) pad2
  *                        out 40: kind (0 miss, 1 surface vertex, 2 emitter front, 3 emitter back), new vertex (25), next direction3,
  *                        NextVertex.flux3, NextVertex.singlePdf, seed', done, emitter radiance3 (lightStraghtHit), t_hit, pad
+ *   SPCBPT_UNIT_SKY_MISS in 32: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf escape direction3 (towards the sky)
+ *                        out 6: contribution rgb of the eye path that sees the sky (SPCBPT_ENV_EYE_SEES_SKY), its RMIS weight
+ *                        (1 / RMIS_pointer), the sky's subspace label, pad.  Needs an environment map (else SPCBPT_ERR_STATE).
  * The ray of EYE_STEP starts at the last vertex's position.  Host pointers; returns after the kernel has run. */
 typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-path vertex carries (BDPTVertex.h:9-70) */
     float position[3], normal[3], flux[3], color[3], last_position[3], rmis3[3];
@@ -404,7 +424,7 @@ typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-pa
     int32_t material_id, subspace_id, depth, last_zone_id;
 } spcbpt_unit_eye_vertex;
 enum spcbpt_unit_op { SPCBPT_UNIT_BSDF = 0, SPCBPT_UNIT_TREE = 1, SPCBPT_UNIT_STAGE1 = 2, SPCBPT_UNIT_BSEARCH = 3, SPCBPT_UNIT_STAGE2 = 4,
-                      SPCBPT_UNIT_UNIFORM = 5, SPCBPT_UNIT_CONNECT = 6, SPCBPT_UNIT_EYE_STEP = 7 };
+                      SPCBPT_UNIT_UNIFORM = 5, SPCBPT_UNIT_CONNECT = 6, SPCBPT_UNIT_EYE_STEP = 7, SPCBPT_UNIT_SKY_MISS = 8 };
 int spcbpt_debug_unit(spcbpt_ctx* ctx, int op, const uint32_t* in, int in_words, uint32_t* out, int out_words, int n,
                       const float* aux, int aux_floats);
 

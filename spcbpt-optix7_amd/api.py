@@ -18,6 +18,9 @@ import numpy as np
 NUM_SUBSPACE = 1000
 NUM_SUBSPACE_LIGHTSOURCE = 200
 CONNECTION_N = 3
+# spcbpt_set_environment_mode flags (include/spcbpt.h)
+ENV_EYE_SEES_SKY = 1
+ENV_PT_SKY_SHADOW_ALONG_DIR = 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libspcbpt_hip.so")
@@ -497,6 +500,8 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_lvc_import": [vp, vp, i32, i32],
         "spcbpt_set_environment": [vp, vp, i32, i32, vp, C.c_float],
         "spcbpt_get_environment": [vp, C.POINTER(i32), C.POINTER(i32), f32p, C.POINTER(C.c_float), C.POINTER(i32)],
+        "spcbpt_set_environment_mode": [vp, i32],
+        "spcbpt_get_environment_mode": [vp, C.POINTER(i32)],
         "spcbpt_hdr_load": [C.c_char_p, C.POINTER(i32), C.POINTER(i32), vp, C.c_size_t],
         "spcbpt_lvc_set_capacity": [vp, i32],
         "spcbpt_lvc_get_capacity": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -586,7 +591,7 @@ def load_library(path: str = LIB_PATH):
 EXPORTED_SYMBOLS = [
     "spcbpt_create", "spcbpt_destroy", "spcbpt_last_error", "spcbpt_set_camera", "spcbpt_set_camera_lookat",
     "spcbpt_resize", "spcbpt_set_subspace", "spcbpt_set_light_trace", "spcbpt_launch", "spcbpt_launch_eye_batch", "spcbpt_launch_light_batch", "spcbpt_build_sampler", "spcbpt_build_sampler_batch",
-    "spcbpt_lvc_export", "spcbpt_lvc_import", "spcbpt_lvc_set_capacity", "spcbpt_lvc_get_capacity", "spcbpt_set_environment", "spcbpt_get_environment", "spcbpt_hdr_load", "spcbpt_lvc_read", "spcbpt_sampler_read", "spcbpt_read_accum",
+    "spcbpt_lvc_export", "spcbpt_lvc_import", "spcbpt_lvc_set_capacity", "spcbpt_lvc_get_capacity", "spcbpt_set_environment", "spcbpt_get_environment", "spcbpt_set_environment_mode", "spcbpt_get_environment_mode", "spcbpt_hdr_load", "spcbpt_lvc_read", "spcbpt_sampler_read", "spcbpt_read_accum",
     "spcbpt_read_frame", "spcbpt_accum_device_ptr", "spcbpt_clear_accum", "spcbpt_get_counters",
     "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench",
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
@@ -835,7 +840,14 @@ class Renderer:
         c3 = np.zeros(3, np.float32)
         r = C.c_float()
         self._chk(self.lib.spcbpt_get_environment(self.h, C.byref(w), C.byref(h), _fp(c3), C.byref(r), C.byref(n)), "get_environment")
-        return dict(width=w.value, height=h.value, center=c3, radius=r.value, n_lights=n.value)
+        f = C.c_int()
+        self._chk(self.lib.spcbpt_get_environment_mode(self.h, C.byref(f)), "get_environment_mode")
+        return dict(width=w.value, height=h.value, center=c3, radius=r.value, n_lights=n.value, flags=f.value)
+
+    def set_environment_mode(self, flags: int):
+        """spcbpt_set_environment_mode: ENV_EYE_SEES_SKY (1) = escaped "SPCBPT_eye" eye sub-paths see the sky (rmis::light_hit_env,
+        corrected sign); ENV_PT_SKY_SHADOW_ALONG_DIR (2) = "pt"'s sky shadow ray ends at P + d 2r.  0 = upstream's behaviour."""
+        self._chk(self.lib.spcbpt_set_environment_mode(self.h, int(flags)), "set_environment_mode")
 
     def lvc_set_capacity(self, vertices: int):
         """Vertices per buffer set, fixed by hand (0 = sized from a probe pass: spcbpt_lvc_set_capacity)."""

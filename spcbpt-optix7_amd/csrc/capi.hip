@@ -305,6 +305,21 @@ int spcbpt_get_environment(spcbpt_ctx* c, int* width, int* height, float center[
     if (n_lights) *n_lights = c->n_lights;
     return SPCBPT_OK;
 }
+int spcbpt_set_environment_mode(spcbpt_ctx* c, int flags) {
+    CTX_CHECK(c);
+    if (flags & ~(SPCBPT_ENV_EYE_SEES_SKY | SPCBPT_ENV_PT_SKY_SHADOW_ALONG_DIR)) { c->error = "set_environment_mode: unknown flag bits"; return SPCBPT_ERR_INVALID_ARG; }
+    if (c->deferred.active) { c->error = "set_environment_mode: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
+    if (c->sync_all()) return SPCBPT_ERR_HIP;
+    c->kp.scene.env.mode = flags;
+    c->blocks_per_cu[0] = c->blocks_per_cu_batch = 0;   // the timed eye launches may change instantiation: ask again
+    return SPCBPT_OK;
+}
+int spcbpt_get_environment_mode(spcbpt_ctx* c, int* flags) {
+    CTX_CHECK(c);
+    if (!flags) return SPCBPT_ERR_INVALID_ARG;
+    *flags = c->kp.scene.env.mode;
+    return SPCBPT_OK;
+}
 
 int spcbpt_set_light_trace(spcbpt_ctx* c, const spcbpt_light_trace_params* p) {
     CTX_CHECK(c);

@@ -12,6 +12,12 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
     if (!d_accum) { error = "render before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!have_camera) { error = "render before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
     if (spcbpt_alg && (!have_sampler || !have_subspace)) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
+    // the counting forms of the eye kernel know no sky strategy: a counted frame would render without it
+    if (spcbpt_alg && !full_mis && kernel_variant() != 0 && eye_sees_sky(kp)) {
+        error = "SPCBPT_eye: the event-counting eye kernels (counters enabled, or classifier trees with direction nodes) do not evaluate the "
+                "eye-sees-sky strategy: clear SPCBPT_ENV_EYE_SEES_SKY (spcbpt_set_environment_mode) for this launch";
+        return SPCBPT_ERR_STATE;
+    }
     if (rs < 1) rs = 1;
     if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
     kp.subframe = frame; kp.row_begin = r0; kp.row_end = std::min(r1, (int)kp.height); kp.row_step = rs;
@@ -44,7 +50,7 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
         HIP_TRY(this, hipMemsetAsync(d_work_counter + rk, 0, sizeof(uint32_t), rstream));
         const int generic = kernel_variant();
         if (!blocks_per_cu[generic]) {
-            blocks_per_cu[generic] = spcbpt_blocks_per_cu(generic, false, kp.scene.general != 0);
+            blocks_per_cu[generic] = spcbpt_blocks_per_cu(generic, false, kp.scene.general != 0, eye_sees_sky(kp));
             // developer knob (occupancy experiments): fewer resident blocks per CU than the kernel's resources allow
             if (const char* e = getenv("SPCBPT_BLOCKS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < blocks_per_cu[generic]) blocks_per_cu[generic] = v; }
             if (const char* e = getenv("SPCBPT_TILES_PER_WAVE")) tiles_per_wave = std::max(1, atoi(e));
@@ -148,7 +154,7 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
     kp.work_counter = d_work_counter + rk;
     kp.result = nullptr; kp.subframe = subframes[0];
     HIP_TRY(this, hipMemsetAsync(d_work_counter + rk, 0, sizeof(uint32_t), rstream));
-    if (!blocks_per_cu_batch) blocks_per_cu_batch = spcbpt_blocks_per_cu(0, true, kp.scene.general != 0);
+    if (!blocks_per_cu_batch) blocks_per_cu_batch = spcbpt_blocks_per_cu(0, true, kp.scene.general != 0, eye_sees_sky(kp));
     int max_blocks = num_cus * blocks_per_cu_batch;
     // a batch kernel runs for tens of milliseconds: the light passes of the batches after it need block slots meanwhile -- few,
     // since they run as a thin grid (launch_light_batch): 97 % (64 steps on one GPU: 5.76 ms per step at 94 %, 5.69 at 97, 5.67 at 100;

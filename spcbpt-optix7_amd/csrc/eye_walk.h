@@ -117,6 +117,50 @@ SPC_DEV f3 eye_emitter_hit(const KParams& p, const Geom& g, float t_hit, f3 ray_
     return is_invalid(ans) ? mk3(0.0f) : ans;
 }
 
+// An eye path that leaves the scene in direction `ray_dir` and sees the environment map (spcbpt_set_environment_mode, bit
+// SPCBPT_ENV_EYE_SEES_SKY): the ENV_MISS vertex of trace_subpath's test knob (oracle: spcbpt_ref.h env_miss_strategy) with
+// rmis::light_hit_env (rmis.h:325-358), the flux multiplier of the eye vertex taken towards the sky (upstream's copy of light_hit
+// takes it with the sign of the emitter case: HISTORY q1).  The virtual light is a direction: no 1 / t^2, no cosine at the sky.
+// Upstream leaves this strategy uncalled (__miss__BDPTVertex ends the path), although the weights of the other sky strategies count it.
+// w_out / label_out: the strategy's RMIS weight (1 / RMIS_pointer) and the sky's subspace (per-function harness only).
+template <bool COUNT, bool CACHE = false, bool ENV = true>
+SPC_DEV f3 eye_sky_miss(const KParams& p, f3 ray_dir, bool last_is_origin, const EyeVertex& last, const WalkState& w, Counts<COUNT>& cn,
+                        float* w_out = nullptr, int* label_out = nullptr) {
+    const DeviceScene& S = p.scene;
+    const f3 Le = env_color(S.env, ray_dir);
+    const float light_pdf = env_pdf(S.env, ray_dir) / (float)S.n_lights;
+    const int label = env_label(S.env, ray_dir);
+    const float pdf_G = fabsf(dot(last.c.n, ray_dir));
+    const f3 flux = last_is_origin ? last.flux * pdf_G * Le : w.next_flux * last.flux * pdf_G * Le;
+    const float singlePdf = w.next_single_pdf * pdf_G / fabsf(dot(last.c.n, ray_dir));
+    const float pdf = last.pdf * singlePdf;
+    float rmis_pointer = 1.0f;
+    if (last.depth + 1 != 1) {
+        // light_hit_env(eye = last, light = the direction: normal -ray_dir, flux Le, pdf = singlePdf = light_pdf)
+        const f3 lflux = Le / light_pdf;
+        const Pbr mat_e = load_pbr_colored(S, last.c.mat, last.c.color);
+        const f3 LB = normalize(last.c.lastPos - last.c.pos);
+        const float LL_pdf_A = rmis_last_pdf(mat_e, last.c, ray_dir);
+        const f3 fm0 = rmis_flux_multiplier<ENV>(mat_e, last.c, ray_dir, LB);
+        int light_label = CACHE ? last.lsub : 0;   // (unused at depth 1)
+        if (!CACHE && last.depth != 1) light_label = tree_label(p.light_tree, last.c.pos, last.c.n, ray_dir, cn);   // tracing_weight_eye: inver_dir = -Mid.normal (rmis.h:141)
+        const float wA = rmis_weight_eye_l(p, last.depth, last.lastZone, light_label, cn);
+        const f3 D_A_0 = last.R3 * LL_pdf_A * fm0 + mk3(wA);
+        const float pdf_A = S.env.project_pdf * fabsf(dot(-ray_dir, last.c.n));          // getPdf_from_light_source, direction branch (183-187)
+        const float fm1 = (float)(1.0 / S.env.project_pdf);
+        const float D_A = sum3(D_A_0 * pdf_A * fm1 * lflux / last.singlePdf);
+        const float weight = sum3(gamma_ss(p, last.sub, label, cn) * lflux * (float)SPCBPT_CONNECTION_N);
+        const float D_B = 1.0f;
+        const float pdf_B = bsdf_pdf(mat_e, last.c.n, LB, ray_dir) * rr_of(last.c.color);   // getPdf(eye, light, LB), end is a direction (158-162)
+        const float lh = D_B / ((weight + D_A) / pdf_B * light_pdf + D_B);
+        rmis_pointer = 1.0f / lh;
+    }
+    if (w_out) *w_out = 1.0f / rmis_pointer;
+    if (label_out) *label_out = label;
+    const f3 ans = flux / pdf / rmis_pointer;
+    return is_invalid(ans) ? mk3(0.0f) : ans;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Pixel of work-slot `slot` (0..63) of tile `tile`: tiles are 8x8 pixels, enumerated x-major inside the selected bands.
 SPC_DEV bool tile_pixel(const KParams& p, uint32_t tile, uint32_t slot, uint32_t& x, uint32_t& y) {

@@ -10,7 +10,8 @@ namespace spc {
 int render_thread_count(const KParams& p);
 int spcbpt_block_threads();   // threads per block of the eye megakernel (kernels.hip: EYE_BLOCK)
 void launch_spcbpt(const KParams& p, int variant, int max_blocks, hipStream_t s);   // 0 timed, 1 reference order + counters (generic), 2 timed + counters
-int spcbpt_blocks_per_cu(int variant, bool batch, bool general);
+int spcbpt_blocks_per_cu(int variant, bool batch, bool general, bool sky);   // sky: eye_sees_sky (the k_spcbpt_sky forms)
+bool eye_sees_sky(const KParams& p);
 int render_tile_count(const KParams& p);
 void launch_pt(const KParams& p, bool count, hipStream_t s);
 void launch_film_merge(const KParams& p, hipStream_t s);

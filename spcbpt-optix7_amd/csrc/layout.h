@@ -63,7 +63,8 @@ struct DEnv {
     float center[3]; float r;
     int32_t width, height, size, div_level;
     int32_t valid; float project_pdf;   // 1 / (pi r^2)
-    int32_t pad[2];
+    int32_t mode;        // spcbpt_set_environment_mode flags (SPCBPT_ENV_*): in the DEnv padding, so that KParams does not grow
+    int32_t pad[1];
 };
 
 struct DTexture {

@@ -11,6 +11,7 @@
 //   CONNECT   connectVertex_SPCBPT + rmis::general_connection / connection_lightSource   raygen.cu:253-303, rmis.h:212-313
 //   EYE_STEP  traceEyeSubPath + __closesthit__eyeSubpath / _LightSource + rmis::light_hit + lightStraghtHit
 //             (cuProg.h:434-461, hit_program.cu:62-147, 246-340, rmis.h:359-389, raygen.cu:305-317)
+//   SKY_MISS  an escaped eye path that sees the sky: eye_sky_miss = rmis::light_hit_env (rmis.h:325-358), corrected sign (eye_walk.h)
 #include <hip/hip_runtime.h>
 
 #include "device_lib.h"
@@ -140,6 +141,17 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
             stw3(o + 26, w.dir); stw3(o + 29, w.next_flux); stf(o + 32, w.next_single_pdf); o[33] = w.seed; o[34] = w.done ? 1u : 0u;
             stf(o + 38, h.t);
         }
+        break;
+    }
+    case SPCBPT_UNIT_SKY_MISS: {
+        const EyeVertex last = load_eye_vertex(r);
+        WalkState w;
+        w.next_flux = ldw3(r + 25); w.next_single_pdf = ldf(r + 28);
+        w.origin = last.c.pos; w.dir = ldw3(r + 29); w.seed = 0u; w.done = false;
+        float wgt = 0.0f;
+        int label = -1;
+        stw3(o, eye_sky_miss(p, w.dir, last.depth == 0, last, w, cn, &wgt, &label));
+        stf(o + 3, wgt); o[4] = (uint32_t)label; o[5] = 0u;
         break;
     }
     default: break;

@@ -1,7 +1,8 @@
 // Headless driver over the C ABI: the frame sequence of the reference app (OptiXPathTracer/optixPathTracer.cpp main 680-837,
 // preprocessing 552-608, render loop 791-822) without GLFW/GL — loads a `.scene`, builds the LBVH, runs the preprocessing,
-// renders N subframes of "pt" or "SPCBPT_eye" and writes the linear accum buffer as PFM and the tone-mapped frame as PPM.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--out prefix]
+// renders N subframes of "pt" or "SPCBPT_eye" and writes the linear accum buffer as PFM and the tone-mapped frame as PPM.  A scene
+// that names an `env_file` gets its sky (spcbpt_set_environment); --env-mode N sets spcbpt_set_environment_mode (SPCBPT_ENV_* bits).
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -20,11 +21,12 @@ static void die(spcbpt_ctx* c, const char* what, int rc) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
+    int env_mode = 0;
     bool minimal = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
         else if (a == "--frames" && i + 1 < argc) frames = atoi(argv[++i]);
         else if (a == "--train-paths" && i + 1 < argc) train_paths = atoi(argv[++i]);
         else if (a == "--minimal") minimal = true;
+        else if (a == "--env-mode" && i + 1 < argc) env_mode = atoi(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -55,6 +58,16 @@ int main(int argc, char** argv) {
     int nt, nn, depth;
     CHECK(ctx, spcbpt_scene_info(ctx, &nt, &nn, &depth));
     printf("scene: %d triangles, BVH %d nodes depth %d\n", nt, nn, depth);
+    {   // the scene's env_file, if it names one (env_params_setup, optixPathTracer.cpp:431-461)
+        const float* rgba = nullptr;
+        int ew = 0, eh = 0;
+        float center[3], radius = 0.0f;
+        if (spcbpt_scene_file_environment(sf, &rgba, &ew, &eh, center, &radius) == SPCBPT_OK && rgba && ew > 0) {
+            CHECK(ctx, spcbpt_set_environment(ctx, rgba, ew, eh, center, radius));
+            printf("environment map: %dx%d\n", ew, eh);
+        }
+    }
+    CHECK(ctx, spcbpt_set_environment_mode(ctx, env_mode));
     CHECK(ctx, spcbpt_set_camera_lookat(ctx, eye, lookat, up, fov, (float)width / (float)height));
     CHECK(ctx, spcbpt_resize(ctx, width, height));
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 0, 1};
