@@ -208,6 +208,41 @@ typedef struct spcbpt_ctx spcbpt_ctx;
  * software LBVH.  device = HIP device ordinal. */
 int spcbpt_create(const spcbpt_scene_desc* scene, int device, spcbpt_ctx** out);
 
+/* Mesh lights: emissive meshes as area lights.  The reference routes every mesh whose material has |emissive_factor| > 0 to its
+ * emitter hit programs (sutil/Scene.cpp:1739-1743) but has no light sampler for it (lightSample, cuProg.h:554-666, knows QUAD and
+ * ENV), so those programs read a light id nobody set; this completes the route.  One mesh light = all triangles of the scene that
+ * carry `material`, emitting the constant radiance `emission` from their front side -- the side normalize((P1-P0) x (P2-P0)) points
+ * to -- exactly like a quad: single-sided for path rays, opaque to shadow rays, a path that hits it ends.  It is ONE entry of the
+ * light list (after the quads, before the environment map; lights are picked uniformly); inside it a triangle is drawn in
+ * proportion to its area and a point uniformly on it, so its point density is 1 / (sum of the triangle areas).  n_patches >= 1
+ * emitter subspaces come from the same budget as the quads' div_level^2 (200 in all, 100 with an environment map): the triangles
+ * are ordered along a Morton curve of their centroids and cut into n_patches runs of about equal area (fewer if the light has
+ * fewer triangles).  Triangles without area are left out (they stay ordinary surface of `material`).  emissive textures,
+ * two-sided emitters and a power-weighted choice between lights are not built. */
+typedef struct spcbpt_mesh_light {
+    int32_t material;   /* index into spcbpt_scene_desc::materials */
+    float emission[3];
+    int32_t n_patches;
+} spcbpt_mesh_light;
+/* spcbpt_create with mesh lights; scene->n_lights may be 0 when n_mesh_lights >= 1.  SPCBPT_ERR_INVALID_ARG (text: spcbpt_last_error(NULL))
+ * for no light at all, a material out of range / named twice / used by no triangle, n_patches < 1, more than 200 patches in all,
+ * or a light none of whose triangles has area.  spcbpt_create itself and spcbpt_scene_desc are unchanged. */
+int spcbpt_create_lit(const spcbpt_scene_desc* scene, const spcbpt_mesh_light* mesh_lights, int n_mesh_lights, int device, spcbpt_ctx** out);
+/* sizeof(spcbpt_mesh_light) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries). */
+int spcbpt_mesh_light_struct_size(void);
+/* One entry of the context's light list = params.lights (scene_shift.cpp:108-153: quads, then the environment map; here the mesh
+ * lights that complete sutil/Scene.cpp:1739-1743 sit between them): type 0 QUAD / 1 ENV / 2 MESH, emitting area (0 for
+ * ENV), emitting triangles, the label of its first patch subspace (patch k has label first_subspace - k) and the number of patches.
+ * Any pointer may be NULL; SPCBPT_ERR_INVALID_ARG when `light` is not in [0, n_lights) (n_lights: spcbpt_get_environment). */
+int spcbpt_light_info(spcbpt_ctx* ctx, int light, int32_t* type, float* area, int32_t* n_triangles, int32_t* first_subspace, int32_t* n_patches);
+/* The sampling table spcbpt_create_lit builds for ONE mesh light (what lightSample, cuProg.h:554-666, would need for the emitters of
+ * sutil/Scene.cpp:1739-1743 and does not have), without a device: `indices` = 3 x n_triangles vertex indices of the
+ * light's triangles.  Outputs (n_triangles entries of capacity each, any may be NULL), in the order of the table: the input triangle,
+ * its running area fraction (accumulated in double, the last exactly 1), its patch, its area; the summed area; the patches in use.
+ * Returns the number of table entries (triangles with area; 0 = a degenerate light) or a negative spcbpt_status. */
+int spcbpt_mesh_light_table(const float* vertices, int n_vertices, const uint32_t* indices, int n_triangles, int n_patches,
+                            int32_t* tri_out, float* cmf_out, int32_t* patch_out, float* tri_area_out, double* area_out, int* n_patches_out);
+
 /* Frees everything the context owns (the reference never frees). */
 int spcbpt_destroy(spcbpt_ctx* ctx);
 
@@ -413,7 +448,9 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *   SPCBPT_UNIT_CONNECT  in 52: eye vertex (spcbpt_unit_eye_vertex, 25) light vertex (spcbpt_light_vertex, 24) pad3   out 4: connectVertex_SPCBPT rgb, RMIS weight
  *   SPCBPT_UNIT_EYE_STEP in 36: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf seed ray direction3 flags(bit 0: d11) pad2
  *                        out 40: kind (0 miss, 1 surface vertex, 2 emitter front, 3 emitter back), new vertex (25), next direction3,
- *                        NextVertex.flux3, NextVertex.singlePdf, seed', done, emitter radiance3 (lightStraghtHit), t_hit, pad
+ *                        NextVertex.flux3, NextVertex.singlePdf, seed', done, emitter radiance3 (lightStraghtHit), t_hit, pad.
+ *                        For an emitter hit the vertex words hold the LIGHT's record at the hit point, as a light sample of that
+ *                        point would: position, normal, pdf = single_pdf, material_id = light id, subspace_id = its patch label.
  *   SPCBPT_UNIT_SKY_MISS in 32: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf escape direction3 (towards the sky)
  *                        out 6: contribution rgb of the eye path that sees the sky (SPCBPT_ENV_EYE_SEES_SKY), its RMIS weight
  *                        (1 / RMIS_pointer), the sky's subspace label, pad.  Needs an environment map (else SPCBPT_ERR_STATE).
@@ -692,7 +729,8 @@ int spcbpt_scene_file_load(const char* scene_path, const char* data_root, spcbpt
  * reads it (sutil::loadScene + processGLTFNode, sutil/Scene.cpp:119-210, 266-550; never called by the reference app): root
  * nodes = nodes without a parent, transform = parent * matrix^T * T * R * S in fp32, TRIANGLES primitives with POSITION /
  * TEXCOORD_0 / indices, baseColor / metallic / roughness factors, baseColorTexture (binary PPM images only), first perspective
- * camera.  Quad lights come from the caller or from this build's root `extras.spcbpt_quad_lights`.  On failure the message
+ * camera.  Quad lights come from the caller or from this build's root `extras.spcbpt_quad_lights`; emissive materials are
+ * handed out as mesh lights by spcbpt_scene_file_mesh_lights.  On failure the message
  * is written to `error` (may be NULL). */
 int spcbpt_gltf_load(const char* path, spcbpt_scene_file** out, char* error, int error_capacity);
 int spcbpt_scene_file_desc(spcbpt_scene_file* s, spcbpt_scene_desc* desc);
@@ -703,6 +741,12 @@ int spcbpt_scene_file_camera(spcbpt_scene_file* s, float eye[3], float lookat[3]
  * the reference's scene box (optixPathTracer.cpp:458-459; SURVEY q7: only the first third of every OBJ shape's vertices enters it)
  * -- to be handed to spcbpt_set_environment.  The pointers stay valid until spcbpt_scene_file_free. */
 int spcbpt_scene_file_environment(spcbpt_scene_file* scene, const float** rgba, int* width, int* height, float center[3], float* radius);
+/* The mesh lights of a glTF file: one per material with a non-zero `emissiveFactor` that some triangle uses, emission =
+ * emissiveFactor x KHR_materials_emissive_strength.emissiveStrength (default 1) -- what sutil/Scene.cpp:1739-1743 tests, completed
+ * by spcbpt_create_lit.  n_patches = root `extras.spcbpt_mesh_light_patches` (default 4), reduced so that quads and mesh lights fit
+ * the 200 patch subspaces.  emissiveTexture and doubleSided are not honoured (a line in the warnings).  What spcbpt_scene_file_desc
+ * returns does not depend on them; a `.scene` file has none.  The pointer stays valid until spcbpt_scene_file_free. */
+int spcbpt_scene_file_mesh_lights(spcbpt_scene_file* s, const spcbpt_mesh_light** mesh_lights, int* n_mesh_lights);
 const char* spcbpt_scene_file_warnings(spcbpt_scene_file* s);
 int spcbpt_scene_file_free(spcbpt_scene_file* s);
 

@@ -45,6 +45,10 @@ class QuadLight(C.Structure):
                 ("emission", C.c_float * 3), ("div_level", C.c_int32)]
 
 
+class MeshLight(C.Structure):   # spcbpt_mesh_light
+    _fields_ = [("material", C.c_int32), ("emission", C.c_float * 3), ("n_patches", C.c_int32)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("texcoords", C.c_void_p), ("n_vertices", C.c_int32),
                 ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("n_triangles", C.c_int32),
@@ -137,6 +141,17 @@ class Scene:
     camera: dict = field(default_factory=dict)  # eye, lookat, up, fov
     name: str = "scene"
     environment: Optional[dict] = None   # rgba (h, w, 4) f32 as a .hdr stores it (row 0 = top), center (3,), radius: Renderer.set_environment(**scene.environment)
+    # emissive meshes as area lights (spcbpt_create_lit): dicts material (index into `materials`), emission (3,), n_patches (default 4)
+    mesh_lights: List[dict] = field(default_factory=list)
+
+    def mesh_light_array(self):
+        """The ctypes array spcbpt_create_lit takes (at least one element, so that the pointer is never NULL)."""
+        ml = (MeshLight * max(1, len(self.mesh_lights)))()
+        for k, d in enumerate(self.mesh_lights):
+            ml[k].material = int(d["material"])
+            ml[k].emission[:] = [float(x) for x in d["emission"]]
+            ml[k].n_patches = int(d.get("n_patches", 4))
+        return ml
 
     def desc(self):
         """Returns (SceneDesc, keepalive)."""
@@ -206,22 +221,23 @@ def load_scene_file(scene_path: str, data_root: str):
     return _scene_from_handle(lib, h, os.path.basename(scene_path))
 
 
-def load_gltf(path: str, lights=None):
+def load_gltf(path: str, lights=None, emissive=False):
     """Reads a glTF 2.0 file (.gltf / .glb) with the library's C++ reader (spcbpt_gltf_load).  `lights` (list of quad-light
-    dicts) replaces whatever the file's `extras.spcbpt_quad_lights` holds.  Returns (scene, warnings)."""
+    dicts) replaces whatever the file's `extras.spcbpt_quad_lights` holds.  emissive=True: the file's emissive materials become
+    the scene's mesh lights (spcbpt_scene_file_mesh_lights); by default they are ignored, as before.  Returns (scene, warnings)."""
     lib = load_library()
     h = C.c_void_p()
     err = C.create_string_buffer(512)
     rc = lib.spcbpt_gltf_load(path.encode(), C.byref(h), err, 512)
     if rc != 0:
         raise SpcbptError(f"spcbpt_gltf_load({path}) failed ({rc}): {err.value.decode()}")
-    scene, warn = _scene_from_handle(lib, h, os.path.basename(path))
+    scene, warn = _scene_from_handle(lib, h, os.path.basename(path), mesh_lights=emissive)
     if lights is not None:
         scene.lights = list(lights)
     return scene, warn
 
 
-def _scene_from_handle(lib, h, name):
+def _scene_from_handle(lib, h, name, mesh_lights=False):
     try:
         d = SceneDesc()
         lib.spcbpt_scene_file_desc(h, C.byref(d))
@@ -256,10 +272,31 @@ def _scene_from_handle(lib, h, name):
             px = np.ctypeslib.as_array(C.cast(ep, C.POINTER(C.c_float)), shape=(eh.value, ew.value, 4)).copy()
             env = dict(rgba=px, center=ec.copy(), radius=float(er.value))
         warn = lib.spcbpt_scene_file_warnings(h).decode()
+        mls = []
+        if mesh_lights:
+            mp, mn = C.POINTER(MeshLight)(), C.c_int()
+            lib.spcbpt_scene_file_mesh_lights(h, C.byref(mp), C.byref(mn))
+            mls = [dict(material=int(mp[k].material), emission=tuple(mp[k].emission), n_patches=int(mp[k].n_patches)) for k in range(mn.value)]
         return Scene(vertices=V, indices=I, tri_material=M, materials=mats, lights=lights, texcoords=UV, textures=texs,
-                     camera=cam, name=name, environment=env), warn
+                     camera=cam, name=name, environment=env, mesh_lights=mls), warn
     finally:
         lib.spcbpt_scene_file_free(h)
+
+
+def mesh_light_table(vertices, triangles, n_patches):
+    """The sampling table spcbpt_create_lit builds for one mesh light (spcbpt_mesh_light_table; needs no GPU): `triangles` = (n, 3)
+    vertex indices of the light's triangles.  Returns dict tri (table order -> row of `triangles`), cmf, patch, tri_area, area, n_patches."""
+    lib = load_library()
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    i = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    n = i.shape[0]
+    tri, cmf, patch, ta = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    area, npch = C.c_double(), C.c_int32()
+    k = lib.spcbpt_mesh_light_table(v.ctypes.data, v.shape[0], i.ctypes.data, n, int(n_patches), tri.ctypes.data, cmf.ctypes.data,
+                                    patch.ctypes.data, ta.ctypes.data, C.byref(area), C.byref(npch))
+    if k < 0:
+        raise SpcbptError(f"spcbpt_mesh_light_table failed ({k})")
+    return dict(tri=tri[:k].copy(), cmf=cmf[:k].copy(), patch=patch[:k].copy(), tri_area=ta[:k].copy(), area=area.value, n_patches=npch.value)
 
 
 def camera_frame(eye, lookat, up, fov_y_deg, aspect):
@@ -485,6 +522,11 @@ def load_library(path: str = LIB_PATH):
     vp, i32, u32, f32p = C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_float)
     sig = {
         "spcbpt_create": [C.POINTER(SceneDesc), i32, C.POINTER(vp)],
+        "spcbpt_create_lit": [C.POINTER(SceneDesc), C.POINTER(MeshLight), i32, i32, C.POINTER(vp)],
+        "spcbpt_mesh_light_struct_size": [],
+        "spcbpt_light_info": [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
+        "spcbpt_mesh_light_table": [vp, i32, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(i32)],
+        "spcbpt_scene_file_mesh_lights": [vp, C.POINTER(C.POINTER(MeshLight)), C.POINTER(i32)],
         "spcbpt_destroy": [vp],
         "spcbpt_set_camera": [vp, f32p, f32p, f32p, f32p],
         "spcbpt_set_camera_lookat": [vp, f32p, f32p, f32p, C.c_float, C.c_float],
@@ -589,7 +631,7 @@ def load_library(path: str = LIB_PATH):
 
 
 EXPORTED_SYMBOLS = [
-    "spcbpt_create", "spcbpt_destroy", "spcbpt_last_error", "spcbpt_set_camera", "spcbpt_set_camera_lookat",
+    "spcbpt_create", "spcbpt_create_lit", "spcbpt_mesh_light_struct_size", "spcbpt_light_info", "spcbpt_mesh_light_table", "spcbpt_scene_file_mesh_lights", "spcbpt_destroy", "spcbpt_last_error", "spcbpt_set_camera", "spcbpt_set_camera_lookat",
     "spcbpt_resize", "spcbpt_set_subspace", "spcbpt_set_light_trace", "spcbpt_launch", "spcbpt_launch_eye_batch", "spcbpt_launch_light_batch", "spcbpt_build_sampler", "spcbpt_build_sampler_batch",
     "spcbpt_lvc_export", "spcbpt_lvc_import", "spcbpt_lvc_set_capacity", "spcbpt_lvc_get_capacity", "spcbpt_set_environment", "spcbpt_get_environment", "spcbpt_set_environment_mode", "spcbpt_get_environment_mode", "spcbpt_hdr_load", "spcbpt_lvc_read", "spcbpt_sampler_read", "spcbpt_read_accum",
     "spcbpt_read_frame", "spcbpt_accum_device_ptr", "spcbpt_clear_accum", "spcbpt_get_counters",
@@ -619,7 +661,11 @@ class Renderer:
         self.scene = scene
         sd, keep = scene.desc()
         h = C.c_void_p()
-        rc = self.lib.spcbpt_create(C.byref(sd), device, C.byref(h))
+        if scene.mesh_lights:   # emissive meshes (spcbpt_create_lit; a scene of quads only takes the entry it always took)
+            ml = scene.mesh_light_array()
+            rc = self.lib.spcbpt_create_lit(C.byref(sd), ml, len(scene.mesh_lights), device, C.byref(h))
+        else:
+            rc = self.lib.spcbpt_create(C.byref(sd), device, C.byref(h))
         if rc != 0:
             msg = self.lib.spcbpt_last_error(None)
             raise SpcbptError(f"spcbpt_create failed ({rc}): {msg.decode() if msg else ''}")
@@ -950,6 +996,16 @@ class Renderer:
         ms, n = C.c_double(), C.c_int()
         self._chk(self.lib.spcbpt_kernel_time(self.h, name.encode(), C.byref(ms), C.byref(n)), "kernel_time")
         return ms.value, n.value
+
+    def light_info(self):
+        """The context's light list (spcbpt_light_info): dicts type (0 QUAD, 1 ENV, 2 MESH), area, n_triangles, first_subspace, n_patches."""
+        out = []
+        n = self.environment()["n_lights"]
+        for k in range(n):
+            t, a, nt, fs, npch = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32(), C.c_int32()
+            self._chk(self.lib.spcbpt_light_info(self.h, k, C.byref(t), C.byref(a), C.byref(nt), C.byref(fs), C.byref(npch)), "light_info")
+            out.append(dict(type=t.value, area=a.value, n_triangles=nt.value, first_subspace=fs.value, n_patches=npch.value))
+        return out
 
     def scene_info(self):
         a, b, c = C.c_int(), C.c_int(), C.c_int()

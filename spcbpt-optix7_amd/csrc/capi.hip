@@ -1,21 +1,28 @@
 // C ABI (include/spcbpt.h) over the HIP kernels: create / destroy, state, launches by name.  The host side of the reference this
 // replaces is cited per function in include/spcbpt.h.  (Read-backs, counters and test hooks: capi_debug.hip; exchange: capi_exchange.hip.)
 #include "capi_common.h"
+#include "mesh_light.h"
 
 using namespace spc;
 
 static thread_local std::string g_create_error;
 
-extern "C" {
-
-
-int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
+// spcbpt_create (ml == nullptr) and spcbpt_create_lit
+static int create_context(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* ml, int n_ml, int device, spcbpt_ctx** out) {
     if (!sc || !out) { g_create_error = "null argument"; return SPCBPT_ERR_INVALID_ARG; }
     *out = nullptr;
-    if (!sc->vertices || !sc->indices || !sc->tri_material || sc->n_vertices < 3 || sc->n_triangles < 1 || sc->n_materials < 1 ||
-        !sc->materials || sc->n_lights < 1 || !sc->lights) {
-        g_create_error = "scene needs vertices, indices, tri_material, >=1 material and >=1 quad light";
-        return SPCBPT_ERR_INVALID_ARG;
+    if (!ml) {
+        if (!sc->vertices || !sc->indices || !sc->tri_material || sc->n_vertices < 3 || sc->n_triangles < 1 || sc->n_materials < 1 ||
+            !sc->materials || sc->n_lights < 1 || !sc->lights) {
+            g_create_error = "scene needs vertices, indices, tri_material, >=1 material and >=1 quad light";
+            return SPCBPT_ERR_INVALID_ARG;
+        }
+    } else {
+        if (!sc->vertices || !sc->indices || !sc->tri_material || sc->n_vertices < 3 || sc->n_triangles < 1 || sc->n_materials < 1 ||
+            !sc->materials || sc->n_lights < 0 || (sc->n_lights > 0 && !sc->lights) || n_ml < 0 || sc->n_lights + n_ml < 1) {
+            g_create_error = "scene needs vertices, indices, tri_material, >=1 material and >=1 light (quad or mesh)";
+            return SPCBPT_ERR_INVALID_ARG;
+        }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (the MI355X path has no CPU fallback)"; return SPCBPT_ERR_NO_DEVICE; }
@@ -34,6 +41,26 @@ int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
     }
     if (patches > SPCBPT_NUM_SUBSPACE_LIGHTSOURCE) { g_create_error = "sum of div_level^2 exceeds NUM_SUBSPACE_LIGHTSOURCE (200)"; return SPCBPT_ERR_INVALID_ARG; }
     if (sc->n_materials + sc->n_lights > 32767) { g_create_error = "too many materials (int16 material ids)"; return SPCBPT_ERR_INVALID_ARG; }
+    // mesh lights: every named material once, in range, on at least one triangle with area; their patches share the quads' budget
+    std::vector<MeshLightTable> ml_tables((size_t)std::max(n_ml, 0));
+    std::vector<std::vector<int32_t>> ml_tris((size_t)std::max(n_ml, 0));   // scene triangles of the light's material
+    for (int j = 0; j < n_ml; j++) {
+        const spcbpt_mesh_light& m = ml[j];
+        const std::string who = "mesh light " + std::to_string(j);
+        if (m.material < 0 || m.material >= sc->n_materials) { g_create_error = who + ": material index out of range"; return SPCBPT_ERR_INVALID_ARG; }
+        for (int k = 0; k < j; k++) if (ml[k].material == m.material) { g_create_error = who + ": material " + std::to_string(m.material) + " is named twice"; return SPCBPT_ERR_INVALID_ARG; }
+        if (m.n_patches < 1) { g_create_error = who + ": n_patches must be >= 1"; return SPCBPT_ERR_INVALID_ARG; }
+        for (int k = 0; k < 3; k++) if (!(m.emission[k] >= 0.0f) || !std::isfinite(m.emission[k])) { g_create_error = who + ": emission must be finite and >= 0"; return SPCBPT_ERR_INVALID_ARG; }
+        patches += m.n_patches;
+        if (patches > SPCBPT_NUM_SUBSPACE_LIGHTSOURCE) { g_create_error = "sum of div_level^2 and mesh-light n_patches exceeds NUM_SUBSPACE_LIGHTSOURCE (200)"; return SPCBPT_ERR_INVALID_ARG; }
+        std::vector<uint32_t> idx;
+        for (int t = 0; t < sc->n_triangles; t++)
+            if (sc->tri_material[t] == m.material) { ml_tris[(size_t)j].push_back(t); idx.insert(idx.end(), sc->indices + 3 * (size_t)t, sc->indices + 3 * (size_t)t + 3); }
+        if (ml_tris[(size_t)j].empty()) { g_create_error = who + ": material " + std::to_string(m.material) + " is used by no triangle"; return SPCBPT_ERR_INVALID_ARG; }
+        build_mesh_light_table(sc->vertices, idx.data(), (int)ml_tris[(size_t)j].size(), m.n_patches, ml_tables[(size_t)j]);
+        if (ml_tables[(size_t)j].tri.empty() || !((float)ml_tables[(size_t)j].area > 0.0f)) { g_create_error = "degenerate mesh light (" + who + ": no triangle with area)"; return SPCBPT_ERR_INVALID_ARG; }
+    }
+    if (sc->n_materials + sc->n_lights + n_ml > 32767) { g_create_error = "too many materials (int16 material ids)"; return SPCBPT_ERR_INVALID_ARG; }
 
     spcbpt_ctx* c = new spcbpt_ctx();
     c->device = device;
@@ -135,6 +162,54 @@ int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
         I.insert(I.end(), qi, qi + 6);
         TM.push_back((int)mats.size() - 1); TM.push_back((int)mats.size() - 1);
         EM.push_back(1); EM.push_back(1);
+        c->h_light_tris.push_back(2);
+    }
+    // Mesh lights (completing sutil/Scene.cpp:1739-1743, which routes emissive meshes to the emitter programs, with the sampler
+    // cuProg.h:554-666 lacks): the light's triangles get its pseudo-material and corners of their own whose UVs carry the patch
+    // (patch + 0.5 at all three corners, so that the interpolated u floors to the patch whatever the barycentrics round to) --
+    // the label of a hit needs no table, the triangle record stays 64 B.
+    for (int j = 0; j < n_ml; j++) {
+        const MeshLightTable& T = ml_tables[(size_t)j];
+        const int n = (int)T.tri.size();
+        DLight L;
+        memset(&L, 0, sizeof(L));
+        L.area = (float)T.area; L.div_level = T.n_patches; L.ss_base = ss_base; L.id = (int)lights.size(); L.type = 2;
+        for (int k = 0; k < 3; k++) L.emission[k] = ml[j].emission[k];
+        ss_base += T.n_patches;
+        DMaterial d;
+        memset(&d, 0, sizeof(d));
+        d.base_color[0] = d.base_color[1] = d.base_color[2] = 1.0f; d.metallic = 1.0f; d.roughness = 1.0f; d.specular = 0.5f;
+        d.sheen_tint = 0.5f; d.clearcoat_gloss = 1.0f; d.light_id = L.id;
+        mats.push_back(d);
+        const int padded = (n + 7) / 8 * 8 + 8, buckets = mesh_light_guide_buckets(n);
+        std::vector<uint32_t> guide;
+        build_mesh_light_guide(T.cmf, buckets, guide);
+        const size_t rec_off = c->h_etable.size() / 4, cmf_off = rec_off + (size_t)MESH_LIGHT_REC_QUADS * n, guide_off = cmf_off + (size_t)padded / 4;
+        c->h_etable.resize((guide_off + (size_t)buckets / 4) * 4, 0.0f);
+        const int32_t words[6] = {(int32_t)rec_off, (int32_t)cmf_off, (int32_t)guide_off, n, buckets, padded};
+        memcpy(L.corner, words, 12); memcpy(L.u, words + 3, 12);
+        for (int i = 0; i < n; i++) {
+            const int t = ml_tris[(size_t)j][(size_t)T.tri[(size_t)i]];
+            const uint32_t base = (uint32_t)(V.size() / 3);
+            float P[3][3];
+            for (int v = 0; v < 3; v++) {
+                memcpy(P[v], sc->vertices + 3 * (size_t)sc->indices[3 * (size_t)t + v], 12);
+                V.insert(V.end(), P[v], P[v] + 3);
+                UV.push_back((float)T.patch[(size_t)i] + 0.5f); UV.push_back(0.0f);
+                I[3 * (size_t)t + v] = base + (uint32_t)v;
+            }
+            TM[(size_t)t] = (int)mats.size() - 1;
+            EM[(size_t)t] = 1;
+            float* r = &c->h_etable[(rec_off + (size_t)MESH_LIGHT_REC_QUADS * i) * 4];
+            for (int k = 0; k < 3; k++) { r[k] = P[0][k]; r[4 + k] = P[1][k] - P[0][k]; r[8 + k] = P[2][k] - P[0][k]; }
+            r[3] = T.cmf[(size_t)i];
+            memcpy(r + 7, &T.patch[(size_t)i], 4);
+        }
+        float* cm = &c->h_etable[cmf_off * 4];
+        for (int i = 0; i < padded; i++) cm[i] = i < n ? T.cmf[(size_t)i] : 2.0f;
+        memcpy(&c->h_etable[guide_off * 4], guide.data(), (size_t)buckets * 4);
+        lights.push_back(L);
+        c->h_light_tris.push_back(n);
     }
     HostMesh mesh;
     mesh.vertices = V.data(); mesh.texcoords = UV.data(); mesh.indices = I.data(); mesh.tri_material = TM.data(); mesh.tri_emitter = EM.data();
@@ -158,12 +233,10 @@ int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
     c->n_paired = bvh.n_paired;
     CREATE_TRY(dev_alloc(&c->d_tri_orig, bvh.tri_orig.size()));
     CREATE_TRY(dev_alloc(&c->d_mats, mats.size()));
-    CREATE_TRY(dev_alloc(&c->d_lights, lights.size()));
     CREATE_TRY(hipMemcpy(c->d_nodes, bvh.nodes.data(), bvh.nodes.size() * 4, hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_tris, bvh.tris.data(), bvh.tris.size() * 4, hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_tri_orig, bvh.tri_orig.data(), bvh.tri_orig.size() * 4, hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_mats, mats.data(), mats.size() * sizeof(DMaterial), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(c->d_lights, lights.data(), lights.size() * sizeof(DLight), hipMemcpyHostToDevice));
     c->h_lights = lights;
     for (int k = 0; k < 3; k++) { c->bbox_lo[k] = 1e30f; c->bbox_hi[k] = -1e30f; }
     for (size_t i = 0; i < V.size(); i += 3)
@@ -199,6 +272,7 @@ int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
     CREATE_TRY(dev_alloc(&c->d_counters, (size_t)C_COUNT));
     CREATE_TRY(hipMemset(c->d_counters, 0, C_COUNT * sizeof(unsigned long long)));
     memset(&c->kp, 0, sizeof(c->kp));
+    if (c->upload_lights()) { g_create_error = c->error; delete c; return SPCBPT_ERR_HIP; }
     c->kp.scene.nodes = c->d_nodes; c->kp.scene.tris = c->d_tris; c->kp.scene.tri_base = c->n_nodes; c->kp.scene.tri_orig = c->d_tri_orig; c->kp.scene.mats = c->d_mats;
     c->kp.scene.lights = c->d_lights; c->kp.scene.tex = c->d_tex; c->kp.scene.n_lights = c->n_lights; c->kp.scene.n_mats = c->n_mats;
     // the same nodes, one record per child: the quad tail of the pooled traversal pass (device_lib.h) and the traversal A/B harness
@@ -210,12 +284,37 @@ int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) {
     c->kp.scene.fan_tail = getenv("SPCBPT_NO_FAN_TAIL") ? 0 : 1;
     c->kp.scene.general = 0;   // no environment map yet; a flagged material (Pbr::brdf) selects the general kernels as well
     for (const DMaterial& m : mats) if (m.brdf) c->kp.scene.general = 1;
+    if (n_ml > 0) c->kp.scene.general = 1;   // the mesh branch of eye_emitter_hit lives in the general forms only (eye_walk.h)
     c->kp.sampler_counts = c->d_sampler_counts;
     c->kp.diag = c->d_diag;
     c->kp.row_step = 1;
     CREATE_TRY(hipDeviceSynchronize());   // the uploads above went through the default stream; the context's streams do not wait for it
 #undef CREATE_TRY
     *out = c;
+    return SPCBPT_OK;
+}
+
+extern "C" {
+
+int spcbpt_create(const spcbpt_scene_desc* sc, int device, spcbpt_ctx** out) { return create_context(sc, nullptr, 0, device, out); }
+
+int spcbpt_create_lit(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* mesh_lights, int n_mesh_lights, int device, spcbpt_ctx** out) {
+    if (n_mesh_lights < 0 || (n_mesh_lights > 0 && !mesh_lights)) { g_create_error = "create_lit: null mesh-light array"; if (out) *out = nullptr; return SPCBPT_ERR_INVALID_ARG; }
+    static const spcbpt_mesh_light none = {0, {0, 0, 0}, 1};
+    return create_context(sc, n_mesh_lights > 0 ? mesh_lights : &none, n_mesh_lights, device, out);
+}
+int spcbpt_mesh_light_struct_size(void) { return (int)sizeof(spcbpt_mesh_light); }
+
+int spcbpt_light_info(spcbpt_ctx* c, int light, int32_t* type, float* area, int32_t* n_triangles, int32_t* first_subspace, int32_t* n_patches) {
+    CTX_CHECK(c);
+    if (light < 0 || light >= (int)c->h_lights.size()) { c->error = "light_info: light index out of range (" + std::to_string(c->h_lights.size()) + " lights)"; return SPCBPT_ERR_INVALID_ARG; }
+    const DLight& L = c->h_lights[(size_t)light];
+    const DEnv& E = c->kp.scene.env;
+    if (type) *type = L.type;
+    if (area) *area = L.type == 1 ? 0.0f : L.area;
+    if (n_triangles) *n_triangles = light < (int)c->h_light_tris.size() ? c->h_light_tris[(size_t)light] : 0;
+    if (first_subspace) *first_subspace = SPCBPT_NUM_SUBSPACE - 1 - (L.type == 1 ? 0 : L.ss_base);
+    if (n_patches) *n_patches = L.type == 1 ? E.div_level * E.div_level : (L.type == 2 ? L.div_level : L.div_level * L.div_level);
     return SPCBPT_OK;
 }
 

@@ -129,6 +129,9 @@ struct Context {
     float* d_env_tex = nullptr;
     float* d_env_cmf = nullptr;
     std::vector<DLight> h_lights;          // the light list as uploaded (the ENV light is appended to it)
+    std::vector<float> h_etable;           // the emitter-triangle table of the mesh lights (layout.h), uploaded right behind the list
+    std::vector<int> h_light_tris;         // per light: triangles that emit (2 for a quad)
+    int upload_lights();                   // (re)allocates d_lights = h_lights + h_etable and points the kernels' scene at it
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};   // of every vertex handed to spcbpt_create (+ the light quads)
     int set_environment(const float* rgba, int w, int h, const float* center, float radius);
     // film

@@ -195,13 +195,30 @@ int Context::install_subspace(const spcbpt_tree_node* et, int ne, const spcbpt_t
     return 0;
 }
 
+// The light list and, right behind it in the same allocation, the emitter-triangle table of the mesh lights (layout.h): the table's
+// offsets count from its own start, so a list that grows by the ENV entry moves it without rewriting a record.
+int Context::upload_lights() {
+    static_assert(sizeof(DLight) % 16 == 0, "the emitter-triangle table must start on a 16-B boundary");
+    std::vector<unsigned char> blob(h_lights.size() * sizeof(DLight) + h_etable.size() * sizeof(float));
+    memcpy(blob.data(), h_lights.data(), h_lights.size() * sizeof(DLight));
+    if (!h_etable.empty()) memcpy(blob.data() + h_lights.size() * sizeof(DLight), h_etable.data(), h_etable.size() * sizeof(float));
+    dev_free(d_lights);
+    unsigned char* d = nullptr;
+    HIP_TRY(this, dev_alloc(&d, blob.size()));
+    d_lights = reinterpret_cast<DLight*>(d);
+    HIP_TRY(this, hipMemcpy(d_lights, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    n_lights = (int)h_lights.size();
+    kp.scene.lights = d_lights; kp.scene.n_lights = n_lights;
+    return 0;
+}
+
 // The environment map as one more light: env_params_setup (optixPathTracer.cpp:431-461) + the ENV entry and the patch-subspace
 // shift of LightSource_shift (scene_shift.cpp:108-153).
 int Context::set_environment(const float* rgba, int w, int h, const float* center, float radius) {
     if (!rgba || w < 1 || h < 1 || (long long)w * h > (1ll << 26)) { error = "set_environment: bad image"; return SPCBPT_ERR_INVALID_ARG; }
     if (kp.scene.env.valid) { error = "set_environment: the context already has an environment map"; return SPCBPT_ERR_STATE; }
     int patches = 0;
-    for (const DLight& L : h_lights) patches += L.div_level * L.div_level;
+    for (const DLight& L : h_lights) patches += L.type == 2 ? L.div_level : L.div_level * L.div_level;   // (a mesh light: n_patches)
     if (patches > SPCBPT_NUM_SUBSPACE_LIGHTSOURCE / 2) { error = "set_environment: with an environment map the quad lights may use at most 100 patch subspaces (sum of div_level^2)"; return SPCBPT_ERR_INVALID_ARG; }
     for (size_t i = 0; i < (size_t)w * h * 4; i++) if (!std::isfinite(rgba[i])) { error = "set_environment: non-finite texel"; return SPCBPT_ERR_INVALID_ARG; }
     if (sync_all()) return SPCBPT_ERR_HIP;
@@ -218,11 +235,8 @@ int Context::set_environment(const float* rgba, int w, int h, const float* cente
     DLight E;
     memset(&E, 0, sizeof(E));
     E.type = 1; E.id = (int)h_lights.size();   // (Light() leaves id / divLevel / ssBase indeterminate upstream)
-    h_lights.push_back(E);
-    dev_free(d_lights);
-    HIP_TRY(this, dev_alloc(&d_lights, h_lights.size()));
-    HIP_TRY(this, hipMemcpy(d_lights, h_lights.data(), h_lights.size() * sizeof(DLight), hipMemcpyHostToDevice));
-    n_lights = (int)h_lights.size();
+    h_lights.push_back(E);   // last: behind the quads and the mesh lights
+    if (int rc = upload_lights()) return rc;
     DEnv& V = kp.scene.env;
     V.tex = d_env_tex; V.cmf = d_env_cmf;
     V.width = w; V.height = h; V.size = w * h;

@@ -181,6 +181,63 @@ SPC_DEV LightSampleD light_reverse_sample(const DeviceScene& S, const DLight& L,
     s.subspace = SPCBPT_NUM_SUBSPACE - (L.ss_base + xb * L.div_level + yb) - 1;
     return s;
 }
+// ---- mesh lights (DLight::type == 2; layout.h: the emitter-triangle table behind the light list) ---------------------------
+// Upstream routes every mesh with an emissive material to the emitter hit programs (sutil/Scene.cpp:1739-1743) but no light sampler
+// knows such a mesh (cuProg.h:554-666 has QUAD and ENV only); this is the missing sampler.  A triangle is drawn in proportion to its
+// area through the cutpoint search of dev_sampling.h (one guide entry + one aligned window of eight CMF values, nearly always), then a
+// point uniformly on it: the point density is 1 / A, the quad's formula with L.area = A.
+SPC_DEV const float* mesh_light_table(const DeviceScene& S) { return reinterpret_cast<const float*>(S.lights) + (size_t)S.n_lights * (sizeof(DLight) / 4); }
+SPC_DEV int mesh_light_pick(const DeviceScene& S, const DLight& L, float u) {   // the number of CMF entries <= u = the first triangle with u < cmf
+    const float* T = mesh_light_table(S);
+    const int count = __float_as_int(L.u[0]), buckets = __float_as_int(L.u[1]), padded = __float_as_int(L.u[2]);
+    const float* cmf = T + (size_t)__float_as_int(L.corner[1]) * 4;
+    const uint32_t* guide = reinterpret_cast<const uint32_t*>(T + (size_t)__float_as_int(L.corner[2]) * 4);
+    const int g = (int)guide[min((int)(u * (float)buckets), buckets - 1)];
+    const int c0 = max(g - 1, 0);
+    int pos = c0 & ~3;
+    GuideScan s = {pos, -INFINITY, INFINITY};   // (the entries of the first quad in front of c0 are <= u like the one the guide names)
+    do {
+        const float4 q0 = *reinterpret_cast<const float4*>(cmf + pos), q1 = *reinterpret_cast<const float4*>(cmf + pos + 4);
+        guide_window<false>(q0, q1, pos, c0, padded, u, s);
+        pos += SPC_GUIDE_WINDOW;
+    } while (!(s.hi < INFINITY) && pos < padded);
+    return min(s.cnt, count - 1);
+}
+SPC_DEV LightSampleD mesh_light_sample(const DeviceScene& S, const DLight& L, float r0, float r1, float r2) {
+    const int k = mesh_light_pick(S, L, r0);
+    const float* rec = mesh_light_table(S) + (size_t)__float_as_int(L.corner[0]) * 4;
+    const float4 a = ldq(rec, (size_t)k * 3), b = ldq(rec, (size_t)k * 3 + 1), c = ldq(rec, (size_t)k * 3 + 2);
+    const f3 e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
+    const float su = sqrtf(r1);
+    LightSampleD s;
+    s.position = mk3(a.x, a.y, a.z) + (1.0f - su) * e1 + (r2 * su) * e2;
+    s.emission = ld3(L.emission);
+    s.normal = normalize(cross(e1, e2));   // the operations of local_geometry on the same corners: a hit's normal bit for bit
+    s.pdf = (1.0f / L.area) / (float)S.n_lights;
+    s.subspace = SPCBPT_NUM_SUBSPACE - (L.ss_base + __float_as_int(b.w)) - 1;
+    return s;
+}
+// the same record for a point HIT on the light: the triangle's own normal, the patch from the UVs the library gave its emitter
+// triangles (patch + 0.5 at all three corners: capi.hip), no search and no table read
+SPC_DEV LightSampleD mesh_light_at_hit(const DeviceScene& S, const DLight& L, const Geom& g) {
+    LightSampleD s;
+    s.position = g.P;
+    s.emission = ld3(L.emission);
+    s.normal = g.N;
+    s.pdf = (1.0f / L.area) / (float)S.n_lights;
+    s.subspace = SPCBPT_NUM_SUBSPACE - (L.ss_base + min(max((int)floorf(g.u), 0), L.div_level - 1)) - 1;
+    return s;
+}
+// a light sample / an emitter hit of a QUAD or a mesh light
+SPC_DEV LightSampleD area_light_sample(const DeviceScene& S, const DLight& L, uint32_t& seed) {
+    const float r1 = rnd(seed), r2 = rnd(seed);
+    if (L.type == 2) return mesh_light_sample(S, L, rnd(seed), r1, r2);
+    return light_reverse_sample(S, L, r1, r2);
+}
+SPC_DEV LightSampleD area_light_at_hit(const DeviceScene& S, const DLight& L, const Geom& g) {
+    if (L.type == 2) return mesh_light_at_hit(S, L, g);
+    return light_reverse_sample(S, L, g.u, g.v);
+}
 SPC_DEV int pick_light(const DeviceScene& S, uint32_t& seed) {
     return min(max((int)floorf(rnd(seed) * S.n_lights), 0), S.n_lights - 1);
 }

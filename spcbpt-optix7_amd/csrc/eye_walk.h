@@ -86,9 +86,11 @@ SPC_DEV f3 eye_emitter_hit(const KParams& p, const Geom& g, float t_hit, f3 ray_
     const DeviceScene& S = p.scene;
     const int light_id = load_pbr(S, g.mat).light_id;
     const DLight& L = S.lights[light_id];
-    const f3 ln = ld3(L.normal);
+    // a mesh light (type 2) exists in `general` scenes only: the branch is compiled out of the plain forms, like the sky's
+    const bool mesh = ENV && L.type == 2;
+    const f3 ln = mesh ? g.N : ld3(L.normal);   // the hit triangle's own normal
     if (dot(ray_dir, ln) > 0) return mk3(0.0f);
-    const LightSampleD ls = light_reverse_sample(S, L, g.u, g.v);
+    const LightSampleD ls = mesh ? mesh_light_at_hit(S, L, g) : light_reverse_sample(S, L, g.u, g.v);
     const float pdf_G = fabsf(dot(ln, ray_dir) * dot(last.c.n, ray_dir)) / (t_hit * t_hit);
     const f3 flux = last_is_origin ? last.flux * pdf_G * ls.emission : w.next_flux * last.flux * pdf_G * ls.emission;
     const float singlePdf = w.next_single_pdf * pdf_G / fabsf(dot(last.c.n, ray_dir));

@@ -160,8 +160,8 @@ __global__ __launch_bounds__(FBLOCK) void k_spcbpt_no_rmis(const KParams p) {
         depth += 1;
         if (g.emitter) {   // __closesthit__eyeSubpath_LightSource: back side -> no vertex; else the path ends on the emitter
             const DLight& L = S.lights[load_pbr(S, g.mat).light_id];
-            if (dot(ray_dir, ld3(L.normal)) > 0) break;
-            const LightSampleD ls = light_reverse_sample(S, L, g.u, g.v);   // init_vertex_from_lightSample of ReverseSample(hit uv)
+            if (dot(ray_dir, L.type == 2 ? g.N : ld3(L.normal)) > 0) break;
+            const LightSampleD ls = area_light_at_hit(S, L, g);   // init_vertex_from_lightSample of ReverseSample(hit uv)
             PVertex lv;
             lv.pos = ls.position; lv.n = ls.normal; lv.color = mk3(0.0f); lv.flux = ls.emission; lv.pdf = ls.pdf; lv.mat = L.id; lv.sub = ls.subspace; lv.depth = 0;
             path[size++] = lv;

@@ -11,10 +11,13 @@
 //     sutil::Camera's default look-at (0, 0, 0) -- kept, unless the node carries this build's `extras.spcbpt_lookat`.
 // Lights: glTF has no area lights and the reference adds its quad lights in the app, so they come from the caller, or from
 // this build's root-level `extras.spcbpt_quad_lights` = [{position, u, v, emission, divLevel}] (u, v absolute corners as in
-// the .scene format).  Images: binary PPM (uri or bufferView with mimeType image/x-portable-pixmap) -- PNG/JPEG decoding (stb
+// the .scene format).  Emissive MESHES -- how exporters write lights that have a shape -- are collected per material with a
+// non-zero emissiveFactor (x KHR_materials_emissive_strength) as mesh lights and handed out by spcbpt_scene_file_mesh_lights,
+// next to and not inside the desc; the reference tests the same factor (sutil/Scene.cpp:1739) and stops there.  Images: binary PPM (uri or bufferView with mimeType image/x-portable-pixmap) -- PNG/JPEG decoding (stb
 // in the reference) is not rebuilt; such images produce a warning and the material keeps its flat colour.
 // The mesh / transform / camera arithmetic is pinned bit-exactly against the reference's vendored tinygltf + sutil::Matrix4x4 /
 // Quaternion (oracle/_ref/libref_gltf.so, tests/golden/ref_gltf.npz, tests/test_gltf.py).
+#include <algorithm>
 #include <cmath>
 #include <new>
 #include <stdexcept>
@@ -437,6 +440,47 @@ struct Gltf {
         return true;
     }
 
+    // one mesh light per emissive material that a triangle uses; called after the nodes (out->M is complete) and the quad lights
+    void mesh_lights() {
+        const J* ms = arr("materials");
+        const size_t n = ms ? ms->a.size() : 0;
+        const J* ex = root.get("extras");
+        int want = ex ? ex->integer("spcbpt_mesh_light_patches", 4) : 4;
+        if (want < 1) want = 1;
+        for (size_t i = 0; i < n; i++) {
+            const J& m = ms->a[i];
+            const J* ef = m.get("emissiveFactor");
+            float e[3] = {0, 0, 0};
+            if (ef && ef->size() >= 3) for (int k = 0; k < 3; k++) e[k] = (float)ef->a[(size_t)k].n;
+            if (!(e[0] > 0.0f || e[1] > 0.0f || e[2] > 0.0f)) continue;
+            bool used = false;
+            for (int32_t t : out->M) if (t == (int32_t)i) { used = true; break; }
+            if (!used) continue;
+            const J* exts = m.get("extensions");
+            const J* st = exts ? exts->get("KHR_materials_emissive_strength") : nullptr;
+            const float strength = st ? (float)st->num("emissiveStrength", 1.0) : 1.0f;
+            const std::string name = m.str("name", ("#" + std::to_string(i)).c_str());
+            if (m.get("emissiveTexture")) out->warnings += "material " + name + ": emissiveTexture is not honoured (the mesh light emits emissiveFactor x strength); ";
+            const J* ds = m.get("doubleSided");
+            if (ds && ds->t == J::Bool && ds->b) out->warnings += "material " + name + ": doubleSided is not honoured on an emissive material (a mesh light emits from its front side); ";
+            spcbpt_mesh_light l;
+            l.material = (int32_t)i;
+            for (int k = 0; k < 3; k++) l.emission[k] = e[k] * strength;
+            l.n_patches = want;
+            out->mesh_lights.push_back(l);
+        }
+        // fit the patch budget next to the quads (SPCBPT_NUM_SUBSPACE_LIGHTSOURCE; the caller may still replace the quads)
+        int quads = 0;
+        for (const spcbpt_quad_light& q : out->lights) quads += q.div_level * q.div_level;
+        const int nl = (int)out->mesh_lights.size();
+        if (nl > 0) {
+            const int room = SPCBPT_NUM_SUBSPACE_LIGHTSOURCE - quads;
+            int each = std::max(1, std::min(want, room / nl));
+            if (each != want) out->warnings += "mesh lights get " + std::to_string(each) + " patch subspaces each instead of " + std::to_string(want) + " (200 in all); ";
+            for (spcbpt_mesh_light& l : out->mesh_lights) l.n_patches = each;
+        }
+    }
+
     bool run() {
         if (!load_buffers() || !materials()) return false;
         const J* nodes = arr("nodes");
@@ -449,7 +493,9 @@ struct Gltf {
         }
         for (size_t i = 0; i < n; i++)
             if (is_root[i] && !node((int)i, m4_identity(), 0)) return false;
-        return lights();
+        if (!lights()) return false;
+        mesh_lights();
+        return true;
     }
 };
 

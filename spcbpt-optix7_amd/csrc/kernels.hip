@@ -127,7 +127,7 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_pt(const KParams p) {
                 Pbr pbr = load_pbr(S, g.mat);
                 if (g.emitter) {  // __closesthit__lightsource
                     const DLight& L = S.lights[pbr.light_id];
-                    const LightSampleD ls = light_reverse_sample(S, L, g.u, g.v);
+                    const LightSampleD ls = area_light_at_hit(S, L, g);
                     if (dot(dir, ls.normal) <= 0) {
                         float mis = 1.0f;
                         if (depth != 0) {
@@ -160,8 +160,7 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_pt(const KParams p) {
                             current = throughput * emission / lpdf * eval * L_dot_N;
                         }
                     } else {
-                        const float r1 = rnd(seed), r2 = rnd(seed);
-                        const LightSampleD ls = light_reverse_sample(S, L, r1, r2);
+                        const LightSampleD ls = area_light_sample(S, L, seed);
                         const f3 dvec = ls.position - g.P;
                         const float L_dist = sqrtf(dot(dvec, dvec));
                         const f3 Ld = dvec / L_dist;

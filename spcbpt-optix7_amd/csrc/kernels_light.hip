@@ -111,8 +111,7 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_light_trace(const KParams 
                 dir = ls.normal;
                 origin_flags = SPCBPT_LV_DIRECTION;
             } else {
-                const float r1 = rnd(seed), r2 = rnd(seed);
-                ls = light_reverse_sample(S, L, r1, r2);
+                ls = area_light_sample(S, L, seed);   // QUAD, or a mesh light (one more random number: the triangle)
                 const float d1 = rnd(seed), d2 = rnd(seed);  // traceMode
                 const Onb onb(ls.normal);
                 dir = onb.to_world(cosine_sample_hemisphere(d1, d2));

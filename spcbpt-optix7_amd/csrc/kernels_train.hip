@@ -168,11 +168,11 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
         if (g.emitter) {
             const Pbr lm = load_pbr(S, g.mat);
             const DLight& L = S.lights[lm.light_id];
-            if (dot(ray_dir, ld3(L.normal)) > 0) break;                       // back of the emitter: no vertex
+            if (dot(ray_dir, L.type == 2 ? g.N : ld3(L.normal)) > 0) break;   // back of the emitter: no vertex
             if (buffer_size + 1 > 2) {                                        // payload.path.size > 2
                 const float r = rnd(w.seed);                                  // rr_acc_accept
                 if (1.0f / (resample_number + 1) > r) {
-                    const LightSampleD ls = light_reverse_sample(S, L, g.u, g.v);
+                    const LightSampleD ls = area_light_at_hit(S, L, g);
                     pretrace_build_path(S, buffer, buffer_size, nv_from_light(ls), path, conn);
                     resample_number++;
                 }
@@ -185,12 +185,11 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
         buffer[buffer_size] = mid;
         buffer_size++;
         // next-event candidate
-        // QUAD lights only: upstream picks among all lights here too (raygen.cu:820-823) and then reads the sample's position, which
+        // QUAD and mesh lights only: upstream picks among all lights here too (raygen.cu:820-823) and then reads the sample's position, which
         // the ENV branch never sets -- undefined, so the sky is left out of the training pass's next-event candidates
         const int n_quads = S.n_lights - (S.env.valid ? 1 : 0);
         const int lid = min(max((int)floorf(rnd(w.seed) * n_quads), 0), n_quads - 1);
-        const float r1 = rnd(w.seed), r2 = rnd(w.seed);
-        const LightSampleD ls = light_reverse_sample(S, S.lights[lid], r1, r2);
+        const LightSampleD ls = area_light_sample(S, S.lights[lid], w.seed);
         const f3 vis_vec = ls.position - mid.c.pos;
         const float len = sqrtf(dot(vis_vec, vis_vec));
         HitRec sh;

@@ -51,9 +51,20 @@ struct DLight {  // 80 B; Light::QUAD (cuda/Light.h:65-84); u, v are absolute co
     float u[3]; int32_t div_level;
     float v[3]; int32_t ss_base;
     float emission[3]; int32_t id;
-    float normal[3]; int32_t type;   // 0 = QUAD, 1 = ENV (the environment map: every other field unused)
+    float normal[3]; int32_t type;   // 0 = QUAD, 1 = ENV (the environment map: every other field unused), 2 = MESH (below)
 };
 static_assert(sizeof(DLight) == 80, "DLight");
+// A mesh light (type 2) = the triangles of one emissive material (sutil/Scene.cpp:1739-1743 routes them to the emitter programs; the
+// sampler is this build's).  The quad's geometry words hold int32 bit patterns instead: corner[0..2] = where the light's triangle
+// records / CMF / guide table start, u[0..2] = triangle count, guide buckets, CMF entries incl. padding; area = the sum of the
+// triangle areas, div_level = its number of patch subspaces (labels NUM_SUBSPACE - 1 - ss_base - patch), normal unused.
+// The EMITTER-TRIANGLE TABLE sits in the light list's own allocation right behind the DLight records (DeviceScene does not grow),
+// all offsets in 16-B quads from its start:
+//   records  3 quads per triangle, in the order of the CMF: (P0.xyz, cmf) (P1 - P0, patch as int32) (P2 - P0, 0)
+//   cmf      the running area fraction per triangle (accumulated in double; the last entry is exactly 1), padded with 2.0 to a multiple
+//            of eight + eight: read in aligned windows of eight like the sampler's CMFs (dev_sampling.h)
+//   guide    per bucket b of `buckets` (a power of two) the first entry with cmf > b / buckets, uint32
+static const int MESH_LIGHT_REC_QUADS = 3;
 
 // params.sky (envInfo, optixPathTracer.h:98-137): the environment map as a light.  `tex` is the .hdr raster with its rows flipped
 // (HDRLoader::loadTexture), `cmf` the sampling CMF over the raster as read (env_params_setup): device copies owned by the context.
@@ -116,9 +127,9 @@ struct DeviceScene {
     const DMaterial* mats;
     const DLight* lights;
     const DTexture* tex;
-    int32_t n_lights;        // QUAD lights, then the ENV light if the scene has an environment map
+    int32_t n_lights;        // QUAD lights, then the mesh lights, then the ENV light if the scene has an environment map
     int32_t n_mats;
-    int32_t general;         // != 0: the scene has an environment map or a material with `brdf` set -> the timed kernels' ENV = true forms
+    int32_t general;         // != 0: the scene has an environment map, a mesh light or a material with `brdf` set -> the timed kernels' ENV = true forms
     int32_t fan_tail;        // != 0: the shadow rays of the quad tail fan out over the idle quads (device_lib.h: fan_tail)
     int32_t tri_base;        // the PAIR records (lbvh.h: Lbvh::pairs) follow the node records in one allocation: record n_nodes + t of `nodes` is the slot of triangle t
     int32_t pad_tri_base;

@@ -407,6 +407,12 @@ int spcbpt_scene_file_camera(spcbpt_scene_file* s, float eye[3], float lookat[3]
     return SPCBPT_OK;
 }
 
+int spcbpt_scene_file_mesh_lights(spcbpt_scene_file* s, const spcbpt_mesh_light** mesh_lights, int* n_mesh_lights) {
+    if (!s || !mesh_lights || !n_mesh_lights) return SPCBPT_ERR_INVALID_ARG;
+    *mesh_lights = s->mesh_lights.empty() ? nullptr : s->mesh_lights.data();
+    *n_mesh_lights = (int)s->mesh_lights.size();
+    return SPCBPT_OK;
+}
 const char* spcbpt_scene_file_warnings(spcbpt_scene_file* s) { return s ? s->warnings.c_str() : ""; }
 
 int spcbpt_scene_file_free(spcbpt_scene_file* s) {

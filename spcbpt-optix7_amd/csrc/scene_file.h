@@ -12,6 +12,7 @@ struct spcbpt_scene_file {
     std::vector<int32_t> M;
     std::vector<spcbpt_material> materials;
     std::vector<spcbpt_quad_light> lights;
+    std::vector<spcbpt_mesh_light> mesh_lights;   // glTF: one per emissive material in use (spcbpt_scene_file_mesh_lights)
     std::vector<std::vector<uint8_t>> tex_pixels;
     std::vector<spcbpt_texture> textures;
     float eye[3] = {0, 0, 0}, lookat[3] = {0, 0, -1}, up[3] = {0, 1, 0};

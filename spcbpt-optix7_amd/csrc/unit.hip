@@ -129,10 +129,13 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
         const bool last_is_origin = last.depth == 0;
         if (g.emitter) {
             const DLight& L = p.scene.lights[load_pbr(p.scene, g.mat).light_id];
-            const bool back = dot(ray_dir, ld3(L.normal)) > 0;
+            const bool back = dot(ray_dir, L.type == 2 ? g.N : ld3(L.normal)) > 0;
             o[0] = back ? 3u : 2u;
             stw3(o + 35, eye_emitter_hit(p, g, h.t, ray_dir, last_is_origin, last, w, cn));
             stf(o + 38, h.t);
+            // the light's record at the hit in the words of the (absent) new vertex: what a light sample of the same point would hold
+            const LightSampleD ls = area_light_at_hit(p.scene, L, g);
+            stw3(o + 1, g.P); stw3(o + 4, ls.normal); stf(o + 19, ls.pdf); stf(o + 20, ls.pdf); o[22] = (uint32_t)L.id; o[23] = (uint32_t)ls.subspace;
         } else {
             EyeVertex mid;
             eye_surface_hit(p, g, h.t, ray_dir, last_is_origin, last, w, mid, cn, (r[33] & 1u) != 0);

@@ -277,6 +277,103 @@ def courtyard(n: int = 6, with_quad_light: bool = True) -> Scene:
     return sc
 
 
+def icosphere(center, radius: float, subdivisions: int = 2):
+    """(vertices (n, 3) f64, triangles (20 * 4^subdivisions, 3)) of a subdivided icosahedron: near-uniform triangles, outward winding."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    v = [np.asarray(x, np.float64) / np.linalg.norm(x) for x in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(subdivisions):
+        mid, nf = {}, []
+
+        def m(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                p = v[a] + v[b]
+                v.append(p / np.linalg.norm(p))
+                mid[k] = len(v) - 1
+            return mid[k]
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    return np.asarray(center, np.float64)[None, :] + radius * np.asarray(v), np.asarray(f, np.uint32)
+
+
+def lamp_floor(lamp_in_view: bool = False) -> Scene:
+    """Mesh-light test scene: one large diffuse floor and, above it, an irregular tetrahedron lamp -- four emitting triangles of clearly
+    different areas and orientations, closed and convex (from any floor point its front-facing faces are unoccluded) -- and nothing
+    else, so the image of the floor is direct light only.  The camera looks straight down at the floor from below the lamp (the
+    lamp outside the frustum); lamp_in_view: from the side, lamp and floor in the frame."""
+    b = _Builder()
+    b.grid((-4, 0, 4), (8, 0, 0), (0, 0, -8), 1, 1, 0)      # floor (normal +y)
+    P = np.array([(-0.6, 1.5, -0.3), (0.6, 1.8, -0.3), (0.0, 1.55, 0.3), (0.35, 2.0, -0.15)], np.float64)   # face areas 0.38 / 0.18 / 0.12 / 0.31
+    faces = [(0, 1, 2), (0, 3, 1), (1, 3, 2), (2, 3, 0)]
+    c = P.mean(0)
+    tris = []
+    for a, bb, cc in faces:   # outward winding
+        n = np.cross(P[bb] - P[a], P[cc] - P[a])
+        tris.append((a, bb, cc) if np.dot(n, P[a] - c) > 0 else (a, cc, bb))
+    b.add(P, np.zeros((4, 2)), tris, 1)
+    mats = [dict(color=(0.7, 0.65, 0.6), roughness=0.5, metallic=0.0), dict(color=(1, 1, 1), roughness=1.0, metallic=0.0)]
+    if lamp_in_view:
+        cam = dict(eye=(0.3, 1.2, 4.5), lookat=(0.05, 1.5, 0.0), up=(0, 1, 0), fov=40.0)
+    else:
+        cam = dict(eye=(0.1, 1.2, 0.05), lookat=(0.1, 0.0, 0.0), up=(0, 0, -1), fov=70.0)
+    sc = b.finish(mats, [], camera=cam, name="lamp_floor")
+    sc.mesh_lights = [dict(material=1, emission=(14.0, 11.0, 8.0), n_patches=4)]
+    return sc
+
+
+def cornell_sphere_lamp(subdivisions: int = 2, n_patches: int = 4) -> Scene:
+    """Mesh-light test scene: the walls and blocks of cornell_box(), closed by a front wall, lit only by an emissive icosphere
+    (20 * 4^subdivisions triangles) that hangs under the ceiling."""
+    b = _Builder()
+    W, R, G, E = 0, 1, 2, 3
+    b.grid((-1, 0, 1), (2, 0, 0), (0, 0, -2), 1, 1, W)
+    b.grid((-1, 2, -1), (2, 0, 0), (0, 0, 2), 1, 1, W)
+    b.grid((-1, 0, -1), (2, 0, 0), (0, 2, 0), 1, 1, W)
+    b.grid((-1, 0, 1), (0, 0, -2), (0, 2, 0), 1, 1, R)
+    b.grid((1, 0, -1), (0, 0, 2), (0, 2, 0), 1, 1, G)
+    b.box((0.1, 0.0, -0.1), (0.7, 0.6, 0.5), W, rot_y=-0.3, skip_bottom=True)
+    b.box((-0.7, 0.0, -0.7), (-0.1, 1.2, -0.1), W, rot_y=0.3, skip_bottom=True)
+    v, f = icosphere((0.05, 1.6, 0.1), 0.22, subdivisions)
+    b.add(v, np.zeros((v.shape[0], 2)), f, E)
+    mats = [dict(color=(0.73, 0.73, 0.73), roughness=0.5, metallic=0.0),
+            dict(color=(0.65, 0.05, 0.05), roughness=0.5, metallic=0.0),
+            dict(color=(0.12, 0.45, 0.15), roughness=0.5, metallic=0.0),
+            dict(color=(1, 1, 1), roughness=1.0, metallic=0.0)]
+    cam = dict(eye=(0.0, 1.0, 5.4), lookat=(0.0, 1.0, 0.0), up=(0, 1, 0), fov=35.0)
+    sc = b.finish(mats, [], camera=cam, name="cornell_sphere_lamp")
+    sc.mesh_lights = [dict(material=E, emission=(9.0, 7.5, 5.0), n_patches=n_patches)]
+    return sc
+
+
+def quad_lights_as_mesh(scene: Scene, n_patches: int = 1) -> Scene:
+    """A copy of `scene` whose quad lights are scene geometry instead: the two triangles the library would append for each quad
+    (corner, corner + u, corner + u + v / corner, corner + u + v, corner + v), under a material of their own named as a mesh light
+    of the same emission."""
+    import copy
+    sc = copy.deepcopy(scene)
+    V, I, M = [np.asarray(sc.vertices, np.float32)], [np.asarray(sc.indices, np.uint32)], [np.asarray(sc.tri_material, np.int32)]
+    UV = [np.zeros((V[0].shape[0], 2), np.float32) if sc.texcoords is None else np.asarray(sc.texcoords, np.float32)]
+    nv = V[0].shape[0]
+    for l in sc.lights:
+        p, u, v = (np.asarray(l[k], np.float32) for k in ("position", "u", "v"))
+        pu, pv = p + u, p + v
+        V.append(np.stack([p, pu, pv, pu + pv - p]).astype(np.float32))
+        UV.append(np.zeros((4, 2), np.float32))
+        I.append(np.array([(nv, nv + 1, nv + 3), (nv, nv + 3, nv + 2)], np.uint32))
+        M.append(np.full(2, len(sc.materials), np.int32))
+        sc.mesh_lights.append(dict(material=len(sc.materials), emission=tuple(l["emission"]), n_patches=n_patches))
+        sc.materials.append(dict(color=(1, 1, 1), roughness=1.0, metallic=0.0))
+        nv += 4
+    sc.vertices, sc.indices, sc.tri_material, sc.texcoords = np.concatenate(V), np.concatenate(I), np.concatenate(M), np.concatenate(UV)
+    sc.lights = []
+    return sc
+
+
 def write_hdr(path: str, rgba: np.ndarray, rle: bool = True, exposure: float = None) -> None:
     """Writes an (h, w, >= 3) float raster as a Radiance RGBE .hdr (new-style RLE scanlines when `rle` and 8 <= w < 32768, else flat):
     the file format HDRLoader reads (scene_shift.cpp:334-500).  A test / authoring helper; mantissas are floor(value / 2^(e - 8))."""
@@ -411,7 +508,9 @@ def write_gltf(scene: Scene, out_dir: str, name: str = "scene", binary: bool = F
     """Writes `scene` as glTF 2.0 (`name`.gltf + `name`.bin + binary-PPM textures, or one `name`.glb when `binary`): one mesh
     with one TRIANGLES primitive per material (float POSITION / TEXCOORD_0, u32 indices), pbrMetallicRoughness factors, a
     perspective camera node, and this build's extensions `extras.spcbpt_quad_lights` (root) / `extras.spcbpt_lookat` (camera
-    node) that csrc/gltf_file.cpp reads back.  Returns the path of the .gltf / .glb file."""
+    node) that csrc/gltf_file.cpp reads back.  A material named by one of the scene's mesh lights gets `emissiveFactor` (and
+    KHR_materials_emissive_strength when a component of the emission exceeds 1) and is written single-sided.  Returns the path of
+    the .gltf / .glb file."""
     import json
     import os
     import struct
@@ -457,7 +556,18 @@ def write_gltf(scene: Scene, out_dir: str, name: str = "scene", binary: bool = F
             images.append({"uri": fn, "mimeType": "image/x-portable-pixmap"})
             textures.append({"source": len(images) - 1})
             pbr["baseColorTexture"] = {"index": len(textures) - 1}
-        mats.append({"name": f"mat{k}", "pbrMetallicRoughness": pbr, "doubleSided": True})
+        mat = {"name": f"mat{k}", "pbrMetallicRoughness": pbr, "doubleSided": True}
+        for ml in getattr(scene, "mesh_lights", []):
+            if int(ml["material"]) == k:
+                e = [float(x) for x in ml["emission"]]
+                strength = max(1.0, max(e))
+                # (a power of two keeps emissiveFactor x strength the emission bit for bit)
+                strength = float(2.0 ** np.ceil(np.log2(strength)))
+                mat["emissiveFactor"] = [x / strength for x in e]
+                if strength != 1.0:
+                    mat["extensions"] = {"KHR_materials_emissive_strength": {"emissiveStrength": strength}}
+                mat["doubleSided"] = False
+        mats.append(mat)
     cam = scene.camera or dict(eye=(0, 0, 5), lookat=(0, 0, 0), up=(0, 1, 0), fov=35.0)
     # the camera node only carries position and up (what the reference's loader reads): a translation, no rotation
     nodes = [{"mesh": 0, "name": "geometry"},
@@ -472,6 +582,9 @@ def write_gltf(scene: Scene, out_dir: str, name: str = "scene", binary: bool = F
            "extras": {"spcbpt_quad_lights": [dict(position=[float(x) for x in l["position"]], u=[float(x) for x in l["u"]],
                                                   v=[float(x) for x in l["v"]], emission=[float(x) for x in l["emission"]],
                                                   divLevel=int(l.get("div_level", 1))) for l in scene.lights]}}
+    if getattr(scene, "mesh_lights", []):
+        doc["extensionsUsed"] = ["KHR_materials_emissive_strength"]
+        doc["extras"]["spcbpt_mesh_light_patches"] = int(scene.mesh_lights[0].get("n_patches", 4))
     if textures: doc["textures"] = textures; doc["images"] = images
     if binary:
         doc["buffers"] = [{"byteLength": len(blob)}]

@@ -2,7 +2,8 @@
 // preprocessing 552-608, render loop 791-822) without GLFW/GL — loads a `.scene`, builds the LBVH, runs the preprocessing,
 // renders N subframes of "pt" or "SPCBPT_eye" and writes the linear accum buffer as PFM and the tone-mapped frame as PPM.  A scene
 // that names an `env_file` gets its sky (spcbpt_set_environment); --env-mode N sets spcbpt_set_environment_mode (SPCBPT_ENV_* bits).
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--out prefix]
+// --emissive: the emissive materials of a glTF file light the scene as mesh lights (spcbpt_create_lit); with them a file needs no quad.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -21,13 +22,13 @@ static void die(spcbpt_ctx* c, const char* what, int rc) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
     int env_mode = 0;
-    bool minimal = false;
+    bool minimal = false, emissive = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -36,6 +37,7 @@ int main(int argc, char** argv) {
         else if (a == "--train-paths" && i + 1 < argc) train_paths = atoi(argv[++i]);
         else if (a == "--minimal") minimal = true;
         else if (a == "--env-mode" && i + 1 < argc) env_mode = atoi(argv[++i]);
+        else if (a == "--emissive") emissive = true;
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -53,8 +55,18 @@ int main(int argc, char** argv) {
     float eye[3], lookat[3], up[3], fov;
     spcbpt_scene_file_camera(sf, eye, lookat, up, &fov, nullptr, nullptr);
     spcbpt_ctx* ctx = nullptr;
-    int rc = spcbpt_create(&desc, 0, &ctx);
+    const spcbpt_mesh_light* mesh_lights = nullptr;
+    int n_mesh_lights = 0;
+    if (emissive) spcbpt_scene_file_mesh_lights(sf, &mesh_lights, &n_mesh_lights);
+    if (emissive && n_mesh_lights == 0) fprintf(stderr, "--emissive: the file has no emissive material in use\n");
+    int rc = n_mesh_lights > 0 ? spcbpt_create_lit(&desc, mesh_lights, n_mesh_lights, 0, &ctx) : spcbpt_create(&desc, 0, &ctx);
     if (rc) die(nullptr, "spcbpt_create", rc);
+    for (int k = 0; k < n_mesh_lights; k++) {
+        int32_t type = 0, tris = 0, first = 0, patches = 0;
+        float area = 0.0f;
+        CHECK(ctx, spcbpt_light_info(ctx, desc.n_lights + k, &type, &area, &tris, &first, &patches));
+        printf("mesh light %d: material %d, %d triangles, area %g, %d patch subspaces from %d down\n", k, mesh_lights[k].material, tris, area, patches, first);
+    }
     int nt, nn, depth;
     CHECK(ctx, spcbpt_scene_info(ctx, &nt, &nn, &depth));
     printf("scene: %d triangles, BVH %d nodes depth %d\n", nt, nn, depth);
