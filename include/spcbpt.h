@@ -454,6 +454,13 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *   SPCBPT_UNIT_SKY_MISS in 32: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf escape direction3 (towards the sky)
  *                        out 6: contribution rgb of the eye path that sees the sky (SPCBPT_ENV_EYE_SEES_SKY), its RMIS weight
  *                        (1 / RMIS_pointer), the sky's subspace label, pad.  Needs an environment map (else SPCBPT_ERR_STATE).
+ *   SPCBPT_UNIT_STAGE2_GUIDED in 6: CONNECTION_N light subspaces, CONNECTION_N random numbers (float bits, in [0, 1))
+ *                        out 12: per connection size, bin (-1: empty subspace, skipped), place in the sorted cache (jump_bias + bin), pmf
+ *                        -- the second-stage draw AS THE EYE MEGAKERNEL RUNS IT (guide table + aligned windows of eight CMF entries,
+ *                        csrc/second_stage_guided.inc.h, the text both compile); STAGE2 above is the reference's bisection.
+ *   SPCBPT_UNIT_SORTED   in 1: place i in the sorted cache (i >= vertex count: zeros)   out 24: the 96 bytes of record i
+ *                        (spcbpt_light_vertex), = the cache's record jump[i]
+ * STAGE2, UNIFORM, STAGE2_GUIDED and SORTED need a built sampler (else SPCBPT_ERR_STATE).
  * The ray of EYE_STEP starts at the last vertex's position.  Host pointers; returns after the kernel has run. */
 typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-path vertex carries (BDPTVertex.h:9-70) */
     float position[3], normal[3], flux[3], color[3], last_position[3], rmis3[3];
@@ -461,7 +468,8 @@ typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-pa
     int32_t material_id, subspace_id, depth, last_zone_id;
 } spcbpt_unit_eye_vertex;
 enum spcbpt_unit_op { SPCBPT_UNIT_BSDF = 0, SPCBPT_UNIT_TREE = 1, SPCBPT_UNIT_STAGE1 = 2, SPCBPT_UNIT_BSEARCH = 3, SPCBPT_UNIT_STAGE2 = 4,
-                      SPCBPT_UNIT_UNIFORM = 5, SPCBPT_UNIT_CONNECT = 6, SPCBPT_UNIT_EYE_STEP = 7, SPCBPT_UNIT_SKY_MISS = 8 };
+                      SPCBPT_UNIT_UNIFORM = 5, SPCBPT_UNIT_CONNECT = 6, SPCBPT_UNIT_EYE_STEP = 7, SPCBPT_UNIT_SKY_MISS = 8,
+                      SPCBPT_UNIT_STAGE2_GUIDED = 9, SPCBPT_UNIT_SORTED = 10 };
 int spcbpt_debug_unit(spcbpt_ctx* ctx, int op, const uint32_t* in, int in_words, uint32_t* out, int out_words, int n,
                       const float* aux, int aux_floats);
 

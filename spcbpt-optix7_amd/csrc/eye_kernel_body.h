@@ -350,77 +350,7 @@
 #if SPC_GUIDE
                     {   // binary_sample (cuProg.h:245-264) of the three through the guide table (device_lib.h: guide_window); every sampler build
                         // writes one (capi.hip: set_guide is allocated with the CMF), so there is no bisection beside it in this build
-                        GuideScan s_[SPCBPT_CONNECTION_N];
-                        int pos_[SPCBPT_CONNECTION_N], first_[SPCBPT_CONNECTION_N];
-                        bool open_[SPCBPT_CONNECTION_N];
-                        uint32_t g_[SPCBPT_CONNECTION_N];
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++)
-                            g_[it] = size_[it] > 0 ? f_guide[bias_[it] + min((int)(u2_[it] * (float)size_[it]), size_[it] - 1)] : 0u;
-#ifndef SPC_GUIDE_SIDE_BY_SIDE
-#define SPC_GUIDE_SIDE_BY_SIDE 0   // 1: the windows of the three connections in flight together (24 registers of CMF values: spills, measured)
-#endif
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                            const int c0 = max((int)g_[it] - 1, 0);
-                            s_[it].cnt = c0; s_[it].lo = -INFINITY; s_[it].hi = INFINITY;
-                            first_[it] = bias_[it] + c0; pos_[it] = first_[it] & ~3;
-                            open_[it] = size_[it] > 0;
-                            if (COUNT && CACHE && open_[it]) cn.add(C_CMF);   // (the guide entry; the reference-order form charges the bisection's probes below)
-                        }
-#if SPC_GUIDE_SIDE_BY_SIDE
-                        bool any_open = false;
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) any_open = any_open || open_[it];
-                        while (any_open) {
-                            float4 a_[SPCBPT_CONNECTION_N], b_[SPCBPT_CONNECTION_N];
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (open_[it]) {
-                                    a_[it] = *reinterpret_cast<const float4*>(f_cmfs + pos_[it]);
-                                    b_[it] = *reinterpret_cast<const float4*>(f_cmfs + pos_[it] + 4);
-                                }
-                            }
-                            any_open = false;
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (open_[it]) {
-                                    if (COUNT && CACHE) cn.add(C_CMF, 8);
-                                    guide_window(a_[it], b_[it], pos_[it], first_[it], bias_[it] + size_[it], u2_[it], s_[it]);
-                                    pos_[it] += 8;
-                                    open_[it] = !(s_[it].hi < INFINITY) && pos_[it] < bias_[it] + size_[it];
-                                }
-                                any_open = any_open || open_[it];
-                            }
-                        }
-#else
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                            while (open_[it]) {
-                                const float4 a = *reinterpret_cast<const float4*>(f_cmfs + pos_[it]);
-                                const float4 b = SPC_GUIDE_WINDOW == 8 ? *reinterpret_cast<const float4*>(f_cmfs + pos_[it] + 4) : a;
-                                if (COUNT && CACHE) cn.add(C_CMF, SPC_GUIDE_WINDOW);
-                                guide_window(a, b, pos_[it], first_[it], bias_[it] + size_[it], u2_[it], s_[it]);
-                                pos_[it] += SPC_GUIDE_WINDOW;
-                                open_[it] = !(s_[it].hi < INFINITY) && pos_[it] < bias_[it] + size_[it];
-                            }
-                        }
-#endif
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                            if (size_[it] != 0) {
-                                int k = s_[it].cnt;
-                                if (k >= size_[it]) {   // no entry above u (the build ends every CMF with 1: not reached): the bisection's last bin
-                                    const float* cmf = f_cmfs + bias_[it];
-                                    k = size_[it] - 1;
-                                    pmf2_[it] = k == 0 ? cmf[k] : cmf[k] - cmf[k - 1];
-                                } else {
-                                    pmf2_[it] = k == 0 ? s_[it].hi : s_[it].hi - s_[it].lo;
-                                }
-                                lslot_[it] = bias_[it] + k;   // its record in the sorted cache (what jump[bias + k] names in the cache's own order)
-                                if (COUNT && !CACHE) cn.add(C_CMF, (unsigned)bisection_probes(k, size_[it]));
-                            }
-                        }
+#include "second_stage_guided.inc.h"
                     }
 #else
                     {   // binary_sample (cuProg.h:245-264) of the three, level by level

@@ -52,6 +52,9 @@ __global__ void k_cmf(const double* __restrict__ prefix, const uint32_t* __restr
     const double base = b > 0 ? prefix[b - 1] : 0.0;
     const double total = prefix[e - 1] - base;
     const bool last = i == e - 1;
+    // (differences of ONE double prefix over the whole cache: a subspace 1e8 times lighter than the cache keeps 8 of its 16 digits
+    // -- the cross-check form; k_sb_cmf sums each subspace by itself.  tests/test_gpu_sampler_synthetic.py leaves its 60-decade
+    // cache out of this form for that reason)
     // sum_pmf == 0 gives NaN CMFs in the reference; guarded here: zero-weight subspaces sample uniformly
     float c = total > 0.0 ? (float)((prefix[i] - base) / total) : (float)(i - b + 1) / (float)(e - b);
     if (last) { c = 1.0f; sub[k].sum_pmf = (float)total; }

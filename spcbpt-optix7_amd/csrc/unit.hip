@@ -8,6 +8,9 @@
 //   BSEARCH   binary_sample on a caller-supplied CMF                        cuProg.h:245-264
 //   STAGE2    sampleSecondStage on the current sampler tables                cuProg.h:268-280
 //   UNIFORM   uniformSample on the current sampler tables                    cuProg.h:283-289
+//   STAGE2_GUIDED  the second-stage draw the eye megakernel runs (second_stage_guided.inc.h: guide table + windows), on caller-supplied
+//             random numbers, CONNECTION_N connections per record
+//   SORTED    one record of the sorted cache (k_sb_copy / k_lvc_sorted_copy), the array the eye megakernel fetches light vertices from
 //   CONNECT   connectVertex_SPCBPT + rmis::general_connection / connection_lightSource   raygen.cu:253-303, rmis.h:212-313
 //   EYE_STEP  traceEyeSubPath + __closesthit__eyeSubpath / _LightSource + rmis::light_hit + lightStraghtHit
 //             (cuProg.h:434-461, hit_program.cu:62-147, 246-340, rmis.h:359-389, raygen.cu:305-317)
@@ -101,6 +104,36 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
         float pmf = 0.0f;
         const int slot = uniform_sample(p.jump, p.sampler_counts[0], seed, pmf);
         o[0] = (uint32_t)slot; stf(o + 1, pmf); o[2] = seed;
+        break;
+    }
+    case SPCBPT_UNIT_STAGE2_GUIDED: {
+        // the state the megakernel holds when it reaches the fragment (eye_kernel_body.h): the subspace records loaded, the random
+        // numbers drawn (here: given, so that a test can put one ON a CMF value), nothing sampled yet
+        constexpr bool COUNT = false, CACHE = true;
+        const float* f_cmfs = p.cmfs;
+        const uint32_t* f_guide = p.guide;
+        float pmf2_[SPCBPT_CONNECTION_N], u2_[SPCBPT_CONNECTION_N];
+        int lslot_[SPCBPT_CONNECTION_N], bias_[SPCBPT_CONNECTION_N], size_[SPCBPT_CONNECTION_N];
+#pragma unroll
+        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
+            pmf2_[it] = 0.0f; u2_[it] = 0.0f; lslot_[it] = -1; bias_[it] = 0; size_[it] = 0;
+            const DSubspace ss = p.subspace[min(r[it], (uint32_t)SPCBPT_NUM_SUBSPACE - 1u)];
+            if (ss.size != 0) { bias_[it] = ss.jump_bias; size_[it] = ss.size; u2_[it] = ldf(r + SPCBPT_CONNECTION_N + it); }
+        }
+        {
+#include "second_stage_guided.inc.h"
+        }
+#pragma unroll
+        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
+            o[4 * it] = (uint32_t)size_[it]; o[4 * it + 1] = (uint32_t)(size_[it] != 0 ? lslot_[it] - bias_[it] : -1);
+            o[4 * it + 2] = (uint32_t)lslot_[it]; stf(o + 4 * it + 3, pmf2_[it]);
+        }
+        break;
+    }
+    case SPCBPT_UNIT_SORTED: {
+        if (r[0] >= (uint32_t)p.sampler_counts[0]) break;   // (no such record: the zeros the output was cleared to)
+        const uint32_t* v = reinterpret_cast<const uint32_t*>(p.lvc_sorted + r[0]);
+        for (int k = 0; k < 24; k++) o[k] = v[k];
         break;
     }
     case SPCBPT_UNIT_CONNECT: {

@@ -26,6 +26,13 @@ def reference_bisection(cmf, u):
     return lo
 
 
+def reference_guide(cmf):
+    """KParams::guide of one subspace by its definition: entry j = the first place k with cmf[k] > (j / n)(1 - 2^-20), n - 1 if none."""
+    n = len(cmf)
+    t = np.arange(n, dtype=np.float64) / n * (1.0 - 2.0 ** -20)
+    return np.minimum(np.searchsorted(np.asarray(cmf).astype(np.float64), t, side="right"), n - 1)   # first k with cmf[k] > t
+
+
 def _setup(pkg, ob, lt=(4000, 64, 1)):
     scene = pkg.scenes.bedroom(target_tris=20000, tex_size=32)
     r = pkg.Renderer(scene, 0)
@@ -53,9 +60,7 @@ def test_second_stage_guide_is_its_definition_and_a_lower_bound(gpu, pkg, ob):
         b, n = int(s["jump_bias"]), int(s["size"])
         cmf = cmfs[b:b + n]
         assert cmf[-1] == 1.0 and (np.diff(cmf) >= 0).all()
-        t = np.arange(n, dtype=np.float64) / n * (1.0 - 2.0 ** -20)
-        want = np.minimum(np.searchsorted(cmf.astype(np.float64), t, side="right"), n - 1)   # first k with cmf[k] > t
-        np.testing.assert_array_equal(guide2[b:b + n], want)
+        np.testing.assert_array_equal(guide2[b:b + n], reference_guide(cmf))
         # every random number of a bucket: the bisection's bin is not in front of the guide's place, and one window of eight from the
         # entry before that place nearly always holds it
         u = rng.random(64).astype(np.float32)

@@ -25,7 +25,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
-OP = dict(BSDF=0, TREE=1, STAGE1=2, BSEARCH=3, STAGE2=4, UNIFORM=5, CONNECT=6, EYE_STEP=7)
+OP = dict(BSDF=0, TREE=1, STAGE1=2, BSEARCH=3, STAGE2=4, UNIFORM=5, CONNECT=6, EYE_STEP=7, SKY_MISS=8, STAGE2_GUIDED=9, SORTED=10)
 
 
 def f32(a):
