@@ -290,9 +290,32 @@ int spcbpt_set_light_trace(spcbpt_ctx* ctx, const spcbpt_light_trace_params* p);
  * (8*r, height, N) and gets every N-th band.  row_begin must be a multiple of
  * 8.  For "light trace" frame is lt_params.launch_frame
  * and the row arguments are ignored.  For "pretrace" frame is
- * pr_params.iteration.  Asynchronous. */
+ * pr_params.iteration.  Asynchronous.
+ *
+ * A sixth launch name, "lt": light tracing, the BDPT strategy t = 1 that upstream disables (readme.md:27).  Every vertex of the
+ * light-vertex cache is connected straight to the camera and added to the pixel it lands on (spcbpt_camera_splat below gives
+ * pixel and importance; a shadow ray to the eye decides visibility; box filter; no MIS weight, it is the only strategy of its
+ * image and no clamp is applied).  Same call sequence and preconditions as "SPCBPT_eye" -- film, camera, "light trace" ->
+ * spcbpt_build_sampler -> launch, else SPCBPT_ERR_STATE -- except that the subspace tuple is not read; frame is the subframe index
+ * and the row arguments select 8-row bands as above (a splat that lands outside them is discarded, so ranks with disjoint band
+ * sets render a correctly sharded film from the same cache).  The image converges to what "pt" converges to.  Not with an
+ * environment map (SPCBPT_ERR_STATE: the directly seen sky is not sampled by this estimator, and sky vertices have no position),
+ * not in the deferred / batched launch forms.  The sum uses float atomics: films agree to rounding, not bit for bit, between runs.
+ * Event counters are left untouched; the kernel-time span is "lt". */
 int spcbpt_launch(spcbpt_ctx* ctx, const char* name, uint32_t frame,
                   int row_begin, int row_end, int row_step);
+
+/* The camera as the end of a light sub-path: where `point` lands on a width x height film seen through (eye, U, V, W) -- any
+ * frame spcbpt_set_camera accepts, orthogonal or not -- and the importance "lt" gives it.  With c = point - eye, D = U . (V x W):
+ *   g  = c . (U x V) / D                 (g <= 0: behind the camera)
+ *   dx = (c . (V x W) / D) / g           dy = (c . (W x U) / D) / g           (|dx| >= 1 or |dy| >= 1: outside)
+ *   px = floor((dx + 1) / 2 width)       py = floor((dy + 1) / 2 height)      (row 0 at dy = -1, as the eye rays are generated)
+ *   weight = width height |c / g|^3 / (4 |D|)                                  (the reciprocal solid angle of a pixel along c)
+ * Returns 1 and fills the outputs (any may be NULL) if the point projects inside the image, 0 (nothing written) otherwise.  Host
+ * code, float32, no context and no GPU needed: the function the splat kernel itself calls. */
+int spcbpt_camera_splat(const float eye[3], const float U[3], const float V[3], const float W[3],
+                        int width, int height, const float point[3],
+                        float* dx, float* dy, int* px, int* py, float* weight);
 
 /* Replaces MyThrustOp::LVC_Process (cuda_thrust/device_thrust.cu:241-332):
  * builds cmfs / jump_buffer / Subspace[1000] / vertex_count / path_count from

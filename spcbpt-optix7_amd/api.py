@@ -315,6 +315,20 @@ def camera_frame(eye, lookat, up, fov_y_deg, aspect):
     return U.astype(f), V.astype(f), W.astype(f)
 
 
+def camera_splat(eye, U, V, W, width, height, point):
+    """spcbpt_camera_splat: where `point` lands on a width x height film seen through (eye, U, V, W), and the importance the
+    light-tracing estimator "lt" gives it.  Returns (dx, dy, px, py, weight), or None when the point does not project inside
+    the image.  Host code in float32 -- the function the splat kernel calls; no GPU needed."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W, point)]
+    dx, dy, we = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+    px, py = C.c_int(-1), C.c_int(-1)
+    if not lib.spcbpt_camera_splat(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), int(width), int(height), _fp(a[4]),
+                                   C.byref(dx), C.byref(dy), C.byref(px), C.byref(py), C.byref(we)):
+        return None
+    return dx.value, dy.value, px.value, py.value, we.value
+
+
 def single_leaf_tree(label=0):
     t = np.zeros(1, dtype=TREE_NODE_DTYPE)
     t[0]["leaf"] = 1
@@ -577,6 +591,7 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_enable_kernel_timing": [vp, i32],
         "spcbpt_trace_closest": [vp, vp, i32, vp, vp, vp],
         "spcbpt_trace_any": [vp, vp, i32, vp],
+        "spcbpt_camera_splat": [f32p, f32p, f32p, f32p, i32, i32, f32p, f32p, f32p, C.POINTER(i32), C.POINTER(i32), f32p],
         "spcbpt_preprocess": [vp, i32, i32, i32],
         "spcbpt_set_pretrace": [vp, i32, i32],
         "spcbpt_train_records_count": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -637,7 +652,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_read_frame", "spcbpt_accum_device_ptr", "spcbpt_clear_accum", "spcbpt_get_counters",
     "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench",
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
-    "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any",
+    "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
     "spcbpt_preprocess", "spcbpt_get_subspace", "spcbpt_scene_info", "spcbpt_set_pretrace", "spcbpt_train_records_count",
     "spcbpt_train_records_read", "spcbpt_train_records_import", "spcbpt_train_records_clear", "spcbpt_preprocess_stage",
     "spcbpt_get_gamma", "spcbpt_gltf_load", "spcbpt_scene_file_load", "spcbpt_scene_file_desc", "spcbpt_scene_file_camera",
@@ -733,6 +748,8 @@ class Renderer:
 
     # -- launches -----------------------------------------------------------
     def launch(self, name: str, frame: int, rows=None):
+        """spcbpt_launch: "light trace", "pt", "SPCBPT_eye", "SPCBPT_no_rmis", "pretrace", or "lt" -- light tracing, the light-vertex
+        cache of the last built sampler splatted onto the film (no environment map; float atomics, so not bit-reproducible)."""
         r0, r1, rs = rows if rows is not None else (0, self.height, 1)
         self._chk(self.lib.spcbpt_launch(self.h, name.encode(), frame, r0, r1, rs), f"launch({name})")
 
@@ -1051,7 +1068,9 @@ class Renderer:
 
     # -- the reference's per-frame sequence (optixPathTracer.cpp:791-822) ------
     def render_frame(self, alg: str, subframe: int, launch_frame: Optional[int] = None, rows=None):
-        if alg in ("SPCBPT_eye", "SPCBPT_no_rmis"):
+        """One frame of `alg`; the algorithms that read a light-vertex cache ("SPCBPT_eye", "SPCBPT_no_rmis", "lt") get their light
+        pass (launch frame subframe + 1 unless given) and sampler build first."""
+        if alg in ("SPCBPT_eye", "SPCBPT_no_rmis", "lt"):
             self.launch("light trace", subframe + 1 if launch_frame is None else launch_frame)
             self.build_sampler()
         self.launch(alg, subframe, rows)

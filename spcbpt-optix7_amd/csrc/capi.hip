@@ -453,7 +453,8 @@ int spcbpt_launch(spcbpt_ctx* c, const char* name, uint32_t frame, int r0, int r
     if (alg == "pt") return c->launch_render("pt", false, frame, r0, r1, rs);
     if (alg == "SPCBPT_no_rmis") return c->launch_render("spcbpt_no_rmis", true, frame, r0, r1, rs, true);   // raygen.cu:465: defined upstream, wired to no program group
     if (alg == "pretrace") return c->launch_pretrace(frame);
-    c->error = "unknown algorithm '" + alg + "' (expected \"pt\", \"light trace\", \"SPCBPT_eye\", \"pretrace\" or \"SPCBPT_no_rmis\")";
+    if (alg == "lt") return c->launch_splat(frame, r0, r1, rs);   // light tracing: the cache splatted onto the film (ctx_splat.hip)
+    c->error = "unknown algorithm '" + alg + "' (expected \"pt\", \"light trace\", \"SPCBPT_eye\", \"pretrace\", \"SPCBPT_no_rmis\" or \"lt\")";
     return SPCBPT_ERR_UNKNOWN_ALG;
 }
 

@@ -249,6 +249,11 @@ struct Context {
     hipEvent_t ev_desc[kMaxRender][kDescRing] = {};              // upload out of that pinned slot done
     int desc_gen[kMaxRender] = {};
     int launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs);
+    // "lt" (ctx_splat.hip): the cache of set `eset` splatted onto the film.  One splat buffer (float4 per pixel, summed with float
+    // atomics) per render stream, allocated at the first "lt" launch of that stream after a resize.
+    float* d_splat[kMaxRender] = {};
+    size_t splat_px[kMaxRender] = {};   // pixels d_splat[k] holds
+    int launch_splat(uint32_t frame, int r0, int r1, int rs);
     int finish_frame();
     // preprocess.hip
     Preprocessor* pre = nullptr;

@@ -464,7 +464,7 @@ Context::~Context() {
     for (int s = 0; s < kMaxRender; s++) {
         if (rstreams[s] && rstreams[s] != stream) (void)hipStreamDestroy(rstreams[s]);
         if (ev_merge[s]) (void)hipEventDestroy(ev_merge[s]);
-        dev_free(d_result[s]); dev_free(d_spill_rs[s]);
+        dev_free(d_result[s]); dev_free(d_spill_rs[s]); dev_free(d_splat[s]);
     }
     if (cstream) (void)hipStreamDestroy(cstream);
     if (stream) (void)hipStreamDestroy(stream);

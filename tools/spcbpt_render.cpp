@@ -1,9 +1,11 @@
 // Headless driver over the C ABI: the frame sequence of the reference app (OptiXPathTracer/optixPathTracer.cpp main 680-837,
 // preprocessing 552-608, render loop 791-822) without GLFW/GL — loads a `.scene`, builds the LBVH, runs the preprocessing,
-// renders N subframes of "pt" or "SPCBPT_eye" and writes the linear accum buffer as PFM and the tone-mapped frame as PPM.  A scene
+// renders N subframes of "pt", "SPCBPT_eye" or "lt" and writes the linear accum buffer as PFM and the tone-mapped frame as PPM.  A scene
 // that names an `env_file` gets its sky (spcbpt_set_environment); --env-mode N sets spcbpt_set_environment_mode (SPCBPT_ENV_* bits).
 // --emissive: the emissive materials of a glTF file light the scene as mesh lights (spcbpt_create_lit); with them a file needs no quad.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]
+// --alg lt: light tracing (the light-vertex cache splatted onto the film): a light pass and a sampler build per frame over the minimal
+// tuple, no preprocessing; its Mpaths/s line counts the light paths only.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -22,7 +24,7 @@ static void die(spcbpt_ctx* c, const char* what, int rc) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -85,6 +87,8 @@ int main(int argc, char** argv) {
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 0, 1};
     CHECK(ctx, spcbpt_set_light_trace(ctx, &lt));
     auto t0 = std::chrono::steady_clock::now();
+    const bool lt_alg = alg == "lt";
+    if (lt_alg) CHECK(ctx, spcbpt_set_subspace(ctx, nullptr, 0, nullptr, 0, nullptr, nullptr));   // the light pass labels its vertices; "lt" reads no label
     if (alg == "SPCBPT_eye") {
         if (minimal) CHECK(ctx, spcbpt_set_subspace(ctx, nullptr, 0, nullptr, 0, nullptr, nullptr));
         else CHECK(ctx, spcbpt_preprocess(ctx, train_paths, train_paths, 1));
@@ -93,7 +97,7 @@ int main(int argc, char** argv) {
     printf("preprocessing: %.2f s\n", std::chrono::duration<double>(t1 - t0).count());
     unsigned lt_frame = 1000000;  // continues after the Q passes of the preprocessing like lt_params.launch_frame
     for (int f = 0; f < frames; f++) {
-        if (alg == "SPCBPT_eye") {  // launchLVCTrace (optixPathTracer.cpp:515-522)
+        if (alg == "SPCBPT_eye" || lt_alg) {  // launchLVCTrace (optixPathTracer.cpp:515-522)
             CHECK(ctx, spcbpt_launch(ctx, "light trace", ++lt_frame, 0, 0, 1));
             CHECK(ctx, spcbpt_build_sampler(ctx));
         }
@@ -103,7 +107,7 @@ int main(int argc, char** argv) {
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
     printf("%d subframes of %s at %dx%d: %.3f s, %.2f Mpaths/s\n", frames, alg.c_str(), width, height, sec,
-           ((double)width * height + (alg == "SPCBPT_eye" ? lt.num_core : 0)) * frames / sec / 1e6);
+           (lt_alg ? (double)lt.num_core : (double)width * height + (alg == "SPCBPT_eye" ? lt.num_core : 0)) * frames / sec / 1e6);
     std::vector<float> accum((size_t)width * height * 4);
     std::vector<uint8_t> frame((size_t)width * height * 4);
     CHECK(ctx, spcbpt_read_accum(ctx, accum.data()));
