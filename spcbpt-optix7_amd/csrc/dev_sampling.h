@@ -108,79 +108,18 @@ SPC_DEV int uniform_sample(const int32_t* jump, int vertex_count, uint32_t& seed
 }
 
 // sampleFirstStage (cuProg.h:290-301) = binary_sample over the 1000-entry CMF row of the eye subspace: ten DEPENDENT probes.
-// For a non-decreasing CMF the bisection returns the first bin with u < cmf[bin], i.e. the number of entries <= u, which THREE
-// counting passes find in three round trips of 4 / 2 / 2 independent 16-B loads (layout.h CMF2_*: 16 coarse entries row[64 k + 63],
-// the 8 middle entries row[8 m + 7] of coarse group k, the 8 entries of middle group m).  The two CMF values of the pmf need no
-// fetch of their own: in a non-decreasing row cmf[l] is the smallest value > u of the last group and cmf[l - 1] the largest value
-// <= u among everything the passes have read (the previous entry of the same group, or -- at a group's first entry -- the last
-// entry of the group before, which IS the middle / coarse value in front of the one that was counted).  Same bin, same pmf, same
-// random number; the probe counter (algorithmic bytes) is charged what the bisection would have probed.
-// (Rounds 1-4 ran two levels of 32: 16 loads and two more for the pmf per sample, 54 per vertex; this form reads 8 per sample and,
-// with the coarse level shared by the CONNECTION_N samples of a vertex, 16 per vertex.)
-struct Cmf3 { int count; float lo, hi; };   // entries <= u so far; largest entry <= u (-inf: none); smallest entry > u of the LAST pass
-SPC_DEV void cmf3_pass(float4 q, float u, Cmf3& c) {
-    const float v[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const bool le = v[i] <= u;
-        c.count += le ? 1 : 0;
-        c.lo = fmaxf(c.lo, le ? v[i] : -INFINITY);
-        c.hi = fminf(c.hi, le ? INFINITY : v[i]);
-    }
-}
-// the CONNECTION_N (or fewer) samples of ONE eye subspace with the random numbers u[0 .. N): the coarse quads are fetched once
-template <int N, bool SERIAL = false>   // SERIAL: the middle and fine passes of one sample after the other (fewer registers in flight)
-SPC_DEV void sample_first_stage_n(const float* cmf_gamma2, int eye_subspace, const float u[N], int l[N], float pmf[N]) {
-    const float4* R = reinterpret_cast<const float4*>(cmf_gamma2 + (size_t)eye_subspace * CMF2_ROW);
-    const float4 c0 = R[0], c1 = R[1], c2 = R[2], c3 = R[3];
-    Cmf3 s[N];
-    float4 a[N], b[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        s[i].count = 0; s[i].lo = -INFINITY; s[i].hi = INFINITY;
-        cmf3_pass(c0, u[i], s[i]); cmf3_pass(c1, u[i], s[i]); cmf3_pass(c2, u[i], s[i]); cmf3_pass(c3, u[i], s[i]);
-    }
-    if (SERIAL) {
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            const float4* M = R + CMF2_COARSE / 4 + (size_t)s[i].count * 2;
-            const float4 m0 = M[0], m1 = M[1];
-            s[i].count *= 8; cmf3_pass(m0, u[i], s[i]); cmf3_pass(m1, u[i], s[i]);
-            const float4* F = R + (CMF2_COARSE + CMF2_MID) / 4 + (size_t)s[i].count * 2;
-            const float4 f0 = F[0], f1 = F[1];
-            s[i].count *= 8; s[i].hi = INFINITY;
-            cmf3_pass(f0, u[i], s[i]); cmf3_pass(f1, u[i], s[i]);
-            l[i] = s[i].count;
-            pmf[i] = s[i].count == 0 ? s[i].hi : s[i].hi - s[i].lo;
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) { const float4* M = R + CMF2_COARSE / 4 + (size_t)s[i].count * 2; a[i] = M[0]; b[i] = M[1]; }
-#pragma unroll
-    for (int i = 0; i < N; i++) { s[i].count *= 8; cmf3_pass(a[i], u[i], s[i]); cmf3_pass(b[i], u[i], s[i]); }
-#pragma unroll
-    for (int i = 0; i < N; i++) { const float4* F = R + (CMF2_COARSE + CMF2_MID) / 4 + (size_t)s[i].count * 2; a[i] = F[0]; b[i] = F[1]; }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        s[i].count *= 8; s[i].hi = INFINITY;
-        cmf3_pass(a[i], u[i], s[i]); cmf3_pass(b[i], u[i], s[i]);
-        l[i] = s[i].count;
-        pmf[i] = s[i].count == 0 ? s[i].hi : s[i].hi - s[i].lo;
-    }
-}
+// For a non-decreasing CMF the bisection returns the first bin with u < cmf[bin], i.e. the number of entries <= u, and the two CMF
+// values of the pmf are the smallest value > u and the largest value <= u among the entries read on the way.  (Rounds 1-4 found the
+// count in two levels of 32, round 5 in three counting passes of 4 / 2 / 2 independent 16-B loads -- the coarse and middle levels of
+// the layout.h CMF2_* row; the guided form below replaced both: profiles/r05_experiments.md, sections 3 and 22.)  Same bin, same
+// pmf, same random number; the probe counter (algorithmic bytes) is charged what the bisection would have probed.
 // Guided form (round 5, the cutpoint method): a guide table names, for the bucket (int)(u * buckets) of the random number, a place g
 // that the answer cannot precede (layout.h: KParams::guide, cmf_guide1), and the entries from g - 1 on are read in aligned windows of
 // eight (two 16-B loads) until one is above u: in a non-decreasing CMF the answer is the number of entries <= u, cmf[answer] the
 // smallest entry > u of the last window and cmf[answer - 1] the largest entry <= u read (entry g - 1 is in the first window for that).
 // One guide entry and -- nearly always -- one window per sample instead of 32 values in three round trips (first stage) or one
 // probe per level and two for the pmf (second stage); same bin, same pmf, same random number.
-#ifndef SPC_GUIDE
-#define SPC_GUIDE 1
-#endif
-#ifndef SPC_GUIDE_WINDOW
-#define SPC_GUIDE_WINDOW 8   // 4: windows of one 16-B load (fewer values read, more often a second round trip: measured, section 25)
-#endif
+static constexpr int GUIDE_WINDOW = 8;   // (windows of one 16-B load: fewer values read, more often a second round trip -- no gain, profiles/r05_experiments.md, section 25)
 struct GuideScan { int cnt; float lo, hi; };   // entries <= u so far; the largest of them; the smallest entry > u
 // the entries at places [pos, pos + 8) of an array, of which [first, end) take part.  first - pos <= 3 (pos is first rounded down to a
 // quad, or a later window), so only the first three entries can lie in front of it.  RANGE = false: every entry takes part (the
@@ -190,7 +129,7 @@ template <bool RANGE = true>
 SPC_DEV void guide_window(float4 q0, float4 q1, int pos, int first, int end, float u, GuideScan& s) {
     const float v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
-    for (int i = 0; i < SPC_GUIDE_WINDOW; i++) {
+    for (int i = 0; i < GUIDE_WINDOW; i++) {
         const bool in = !RANGE || ((i >= 3 || pos + i >= first) && pos + i < end);
         const bool le = in && v[i] <= u, gt = in && !(v[i] <= u);
         s.cnt += le ? 1 : 0;
@@ -206,35 +145,13 @@ SPC_DEV int sample_first_stage_guided(const float* cmf_gamma2, const uint16_t* g
     int pos = c0 & ~3, windows = 0;
     GuideScan s = {pos, -INFINITY, INFINITY};   // (the entries of the first quad in front of c0 are counted with it: all <= u)
     do {
-        const float4 q0 = *reinterpret_cast<const float4*>(fine + pos), q1 = SPC_GUIDE_WINDOW == 8 ? *reinterpret_cast<const float4*>(fine + pos + 4) : q0;
+        const float4 q0 = *reinterpret_cast<const float4*>(fine + pos), q1 = *reinterpret_cast<const float4*>(fine + pos + 4);
         guide_window<false>(q0, q1, pos, c0, CMF2_FINE, u, s);
-        pos += SPC_GUIDE_WINDOW; windows++;
+        pos += GUIDE_WINDOW; windows++;
     } while (!(s.hi < INFINITY) && pos < CMF2_FINE);
     l = s.cnt;
     pmf = l == 0 ? s.hi : s.hi - s.lo;
     return windows;
-}
-// ... of the CONNECTION_N samples of one eye subspace: the guide entries in flight together, the windows one after the other
-template <int N>
-SPC_DEV void sample_first_stage_guided_n(const float* cmf_gamma2, const uint16_t* guide1, int eye_subspace, const float u[N], int l[N], float pmf[N], int windows[N]) {
-    const float* fine = cmf_gamma2 + (size_t)eye_subspace * CMF2_ROW + CMF2_COARSE + CMF2_MID;
-    int g[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) g[i] = guide1[(size_t)eye_subspace * CMF_GUIDE1 + (int)(u[i] * (float)CMF_GUIDE1)];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const int c0 = max(g[i] - 1, 0);
-        int pos = c0 & ~3;
-        GuideScan s = {pos, -INFINITY, INFINITY};
-        windows[i] = 0;
-        do {
-            const float4 q0 = *reinterpret_cast<const float4*>(fine + pos), q1 = SPC_GUIDE_WINDOW == 8 ? *reinterpret_cast<const float4*>(fine + pos + 4) : q0;
-            guide_window<false>(q0, q1, pos, c0, CMF2_FINE, u[i], s);
-            pos += SPC_GUIDE_WINDOW; windows[i]++;
-        } while (!(s.hi < INFINITY) && pos < CMF2_FINE);
-        l[i] = s.cnt;
-        pmf[i] = s.cnt == 0 ? s.hi : s.hi - s.lo;
-    }
 }
 SPC_DEV int bisection_probes(int l, int size) {   // the probes of the reference's bisection on its way to bin l
     int n = 0, mid = size / 2 - 1, a = 0, b = size;
@@ -249,19 +166,11 @@ template <bool COUNT, bool EXEC = false>   // EXEC: charge what the guided form 
 SPC_DEV int sample_first_stage(const KParams& p, int eye_subspace, uint32_t& seed, float& pmf, Counts<COUNT>& cn) {
     // a caller-supplied matrix with a decreasing row (not a CMF) keeps the bisection, whose answer is then its own definition
     if (!p.cmf_gamma2) return binary_sample(p.cmf_gamma + (size_t)eye_subspace * SPCBPT_NUM_SUBSPACE, SPCBPT_NUM_SUBSPACE, seed, pmf, cn);
-    const float u[1] = {rnd(seed)};
-    int l[1];
-    float pm[1];
-#if SPC_GUIDE
-    const int windows = sample_first_stage_guided(p.cmf_gamma2, p.cmf_guide1, eye_subspace, u[0], l[0], pm[0]);
-    pmf = pm[0];
-    if (COUNT) cn.add(C_CMF, EXEC ? 1u + (unsigned)SPC_GUIDE_WINDOW * (unsigned)windows : (unsigned)bisection_probes(l[0], SPCBPT_NUM_SUBSPACE));
-#else
-    sample_first_stage_n<1>(p.cmf_gamma2, eye_subspace, u, l, pm);
-    pmf = pm[0];
-    if (COUNT) cn.add(C_CMF, EXEC ? 32u : (unsigned)bisection_probes(l[0], SPCBPT_NUM_SUBSPACE));
-#endif
-    return l[0];
+    const float u = rnd(seed);
+    int l;
+    const int windows = sample_first_stage_guided(p.cmf_gamma2, p.cmf_guide1, eye_subspace, u, l, pmf);
+    if (COUNT) cn.add(C_CMF, EXEC ? 1u + (unsigned)GUIDE_WINDOW * (unsigned)windows : (unsigned)bisection_probes(l, SPCBPT_NUM_SUBSPACE));
+    return l;
 }
 
 }  // namespace spc

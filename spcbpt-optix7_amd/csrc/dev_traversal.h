@@ -99,15 +99,6 @@ SPC_DEV f3 safe_inv(f3 d) {
     r.z = __builtin_amdgcn_rcpf(fabsf(d.z) > tiny ? d.z : copysignf(tiny, d.z));
     return r;
 }
-SPC_DEV bool slab(float4 lo, float4 hi, f3 o, f3 inv, float tmin, float tmax, float& tnear) {
-    float tx0 = (lo.x - o.x) * inv.x, tx1 = (hi.x - o.x) * inv.x;
-    float ty0 = (lo.y - o.y) * inv.y, ty1 = (hi.y - o.y) * inv.y;
-    float tz0 = (lo.z - o.z) * inv.z, tz1 = (hi.z - o.z) * inv.z;
-    float t0 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tmin));
-    float t1 = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), tmax));
-    tnear = t0;
-    return t0 <= t1 * 1.0000004f;
-}
 // Moller-Trumbore on (P0, P1, P2); accepts tmin < t < tmax; culls the back face when asked (emitter quads).
 // The triangle step of the traversal loop runs at ~10 % lane utilisation (a lane sits on a leaf in one iteration out of ten, and
 // nearly every iteration has SOME lane on one), so every instruction here is paid by the whole wave: the cross products may
@@ -141,44 +132,34 @@ SPC_DEV bool tri_test(float4 q0, float4 q1, float4 q2, f3 o, f3 d, float tmin, f
 // "while-while" traversal: all lanes first descend through internal nodes (lanes that already sit on a leaf wait), then
 // the wave processes leaves together, so the two code paths are not interleaved per iteration inside a divergent wave.
 static constexpr int kTravDone = 0x7fffffff;
-#ifndef SPC_QUAD_TAIL
-#define SPC_ONE_FETCH 1
-#ifndef SPC_PRIO_TAIL
-#define SPC_PRIO_TAIL -1  // >= 0: s_setprio at the entry of the quad / fan tails (kernels.hip sets the pass's and resets after it)
-#endif
 #ifndef SPC_TRI_BATCH
 #define SPC_TRI_BATCH 8   // trace_pool: N > 1 = lanes on a leaf wait until N of them are (or nobody is on an internal node) before the triangle step
 #endif
-#ifndef SPC_PROBE_DROP_TAIL
-#define SPC_PROBE_DROP_TAIL 0
-#endif
-#ifndef SPC_TRI_PAIRS
-#define SPC_TRI_PAIRS 1   // trace_pool: a lane's triangle step tests both halves of a fan pair (lbvh.h: Lbvh::pairs); 0 = one triangle per step (the slot's first three corners)
-#endif
-#ifndef SPC_TRI_PAIRS_LANE
-#define SPC_TRI_PAIRS_LANE 1   // traverse<> (one ray per lane to its end: "pt", the light pass, the pre-trace): the same pair step
-#endif
-#ifndef SPC_PROBE_TRI_PAIRS
-#define SPC_PROBE_TRI_PAIRS 0
-#endif
-#ifndef SPC_ROOT_AHEAD
-#define SPC_ROOT_AHEAD 1  // trace_pool: a lane that is about to draw a ray requests the root with the other lanes' next records
-#endif
-#define SPC_QUAD_TAIL 1   // the last <= 16 rays of a pooled pass continue on four lanes each (trace_pool); 0 = the lane loop to the end
-#define SPC_FAN_TAIL 1    // ... and its shadow rays on as many quads as the wave has idle (fan_tail); 0 = one quad per ray to the end
-#endif
-// pop the next stack entry into (node, leaf_count); leaf refs carry their count: 1<<31 | first<<3 | count (count <= 4).
-// A macro, not a lambda: a by-reference capture keeps node / leaf_count in scratch memory inside the loop.
+// A stack word into (node, leaf_count); leaf refs carry their count: 1<<31 | first<<3 | count (count <= 4).
+// Macros, not lambdas: a by-reference capture keeps node / leaf_count in scratch memory inside the loop.
+#define SPC_STACK_DECODE(W, NODE, LEAF)                                                                               \
+    do {                                                                                                              \
+        if ((W) & 0x80000000u) { NODE = ~(int)(((W) & 0x7fffffffu) >> 3); LEAF = (int)((W) & 7u); }                   \
+        else NODE = (int)(W);                                                                                         \
+    } while (0)
+// pop the next stack entry into (node, leaf_count)
 #define SPC_TRAV_POP() SPC_TRAV_POP_(pop)
 #define SPC_TRAV_POP_(POP)                                                                          \
     do {                                                                                            \
         if (st.sp == 0) { node = kTravDone; }                                                       \
         else {                                                                                      \
             const uint32_t w__ = st.POP();                                                          \
-            if (w__ & 0x80000000u) { node = ~(int)((w__ & 0x7fffffffu) >> 3); leaf_count = (int)(w__ & 7u); } \
-            else node = (int)w__;                                                                   \
+            SPC_STACK_DECODE(w__, node, leaf_count);                                                \
         }                                                                                           \
     } while (0)
+// ---- DPP quad_perm helpers (four consecutive lanes) ---------------------------------------------------------------------
+static constexpr int kQBcast0 = 0x00, kQBcast1 = 0x55, kQBcast2 = 0xAA, kQBcast3 = 0xFF;
+static constexpr int kQRot1 = 0x39, kQRot2 = 0x4E, kQRot3 = 0x93, kQXor1 = 0xB1;   // [1,2,3,0] [2,3,0,1] [3,0,1,2] [1,0,3,2]
+template <int CTRL>
+SPC_DEV uint32_t quad_perm(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true); }
+template <int CTRL>
+SPC_DEV float quad_permf(float v) { return __uint_as_float(quad_perm<CTRL>(__float_as_uint(v))); }
+
 // slab test of the 4 quantised child boxes of a node; misses get key 0xffffffff, hits the entry distance with the slot index
 // in the two low mantissa bits (t >= 0, so unsigned order = float order).  plane distance = (org + q s - o) / d
 // = q (s inv) + (org inv - o inv): two per-axis constants per node, then one byte->float convert and one FMA per plane.
@@ -210,14 +191,39 @@ SPC_DEV void slab4q(const float4 q0, const float4 q1, const float4 q2, f3 ood, f
         key[i] = (t0 <= t1 * 1.0000004f) ? ((__float_as_uint(t0) & ~3u) | (uint32_t)i) : 0xffffffffu;
     }
 }
+// ... of ONE child, by lane qr of the four lanes that share a ray (the quad and fan-out tails below, quad_trace.hip): `rec` is record qr
+// of the node in the quad layout (k_repack_nodes_quad: x, y = the child's six plane bytes, w = origin.x / y / z and the scale exponents
+// for qr = 0 .. 3, exchanged by DPP broadcasts).  The same arithmetic and the same key as slab4q.  `hit` is the compare's own result:
+// deriving it from the key afterwards costs a second v_cmp in fan_tail.  Two entry points: slab1q for a caller that needs both, slab1q_key
+// for one that ranks by the key alone.  In the key-only form (HIT = false) the compare has the select as its only use from the start, as
+// it had when the test stood in the caller, and the code is the same to the instruction (with `hit` merely unused, the counting forms
+// of k_spcbpt came out with two instructions swapped); its `hit` field means nothing, which is why only slab1q_key calls it.
+struct QuadSlab { uint32_t key; bool hit; };
+template <bool HIT>
+SPC_DEV QuadSlab slab1q_impl(const float4 rec, f3 inv, f3 ood, float tmin, float tmax, uint32_t qr) {
+    const float ox = quad_permf<kQBcast0>(rec.w), oy = quad_permf<kQBcast1>(rec.w), oz = quad_permf<kQBcast2>(rec.w);
+    const uint32_t e = quad_perm<kQBcast3>(__float_as_uint(rec.w));
+    const float ax = __uint_as_float((e & 0xffu) << 23) * inv.x, ay = __uint_as_float(((e >> 8) & 0xffu) << 23) * inv.y,
+                az = __uint_as_float(((e >> 16) & 0xffu) << 23) * inv.z;
+    const float bx = fmaf(ox, inv.x, -ood.x), by = fmaf(oy, inv.y, -ood.y), bz = fmaf(oz, inv.z, -ood.z);
+    const uint32_t pa = __float_as_uint(rec.x), pb = __float_as_uint(rec.y);
+    const float lx = (float)(pa & 255u), ly = (float)((pa >> 8) & 255u), lz = (float)((pa >> 16) & 255u), hx = (float)(pa >> 24),
+                hy = (float)(pb & 255u), hz = (float)((pb >> 8) & 255u);
+    const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;
+    const float tnx = fmaf(sx ? hx : lx, ax, bx), tfx = fmaf(sx ? lx : hx, ax, bx);
+    const float tny = fmaf(sy ? hy : ly, ay, by), tfy = fmaf(sy ? ly : hy, ay, by);
+    const float tnz = fmaf(sz ? hz : lz, az, bz), tfz = fmaf(sz ? lz : hz, az, bz);
+    const float t0 = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+    const float t1 = fminf(fminf(tfx, tfy), fminf(tfz, tmax));
+    const bool hit = t0 <= t1 * 1.0000004f;
+    return {hit ? ((__float_as_uint(t0) & ~3u) | qr) : 0xffffffffu, HIT && hit};
+}
+SPC_DEV QuadSlab slab1q(const float4 rec, f3 inv, f3 ood, float tmin, float tmax, uint32_t qr) { return slab1q_impl<true>(rec, inv, ood, tmin, tmax, qr); }
+SPC_DEV uint32_t slab1q_key(const float4 rec, f3 inv, f3 ood, float tmin, float tmax, uint32_t qr) { return slab1q_impl<false>(rec, inv, ood, tmin, tmax, qr).key; }
 SPC_DEV uint32_t sel4u(const uint32_t r[4], uint32_t i) {  // two-level select: three v_cndmask, no control flow
     const uint32_t a = (i & 1u) ? r[1] : r[0];
     const uint32_t b = (i & 1u) ? r[3] : r[2];
     return (i & 2u) ? b : a;
-}
-SPC_DEV int sel4i(const float4 q, uint32_t i) {
-    const float v = i == 0 ? q.x : (i == 1 ? q.y : (i == 2 ? q.z : q.w));
-    return __float_as_int(v);
 }
 SPC_DEV uint32_t stack_word(int ref, int count) {
     return ref >= 0 ? (uint32_t)ref : (0x80000000u | ((uint32_t)(~ref) << 3) | (uint32_t)count);
@@ -252,8 +258,7 @@ SPC_DEV uint32_t stack_word(int ref, int count) {
             SPC_TRAV_POP_(POP);                                                                                       \
         } else {                                                                                                      \
             st.PUSH(r1__, k__[1] != 0xffffffffu, r2__, k__[2] != 0xffffffffu, r3__, k__[3] != 0xffffffffu);           \
-            if (r0__ & 0x80000000u) { node = ~(int)((r0__ & 0x7fffffffu) >> 3); leaf_count = (int)(r0__ & 7u); }      \
-            else node = (int)r0__;                                                                                    \
+            SPC_STACK_DECODE(r0__, node, leaf_count);                                                                 \
         }                                                                                                             \
     } while (0)
 #define SPC_CSWAP__(a, b) { const uint32_t lo__ = min(k__[a], k__[b]), hi__ = max(k__[a], k__[b]); k__[a] = lo__; k__[b] = hi__; }
@@ -277,7 +282,7 @@ SPC_DEV bool traverse(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, f3 
     // (A single 64-B fetch per iteration serving node OR triangle lanes loses HERE, where every lane follows one ray to its end:
     // round 1 14.0 against 11.1 ms per frame; round 4, fetched a step ahead: pt frame 4.29 -> 4.43 ms, light pass 1.13 -> 1.16 ms --
     // a lane that reaches a leaf waits a whole iteration for its first triangle.  It WINS in trace_pool, whose triangle step runs
-    // at a tenth of the lanes in 83 % of the iterations: see SPC_ONE_FETCH there.)
+    // at a tenth of the lanes in 83 % of the iterations: see the fetch step there.)
     // The iteration in two instantiations, as in trace_pool: LDS-only stack operations while no lane still in the loop is within three
     // entries of the end of its LDS part (a vote per iteration), the plain ones otherwise.
 #define SPC_TRAVERSE_ITER__(PUSH, POP)                                                                                \
@@ -294,35 +299,22 @@ SPC_DEV bool traverse(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, f3 
             const int tri = ~node;                                                                                    \
             cn.add(C_TRI);                                                                                            \
             SPC_UTIL_COUNT(C_U_TRI_LANES, C_U_TRI_SLOTS)                                                              \
-            bool h;                                                                                                   \
+            /* the triangle's PAIR slot (lbvh.h; behind the node records): both halves of a quad in one step, A first */ \
+            const size_t base = ((size_t)(uint32_t)S.tri_base + (size_t)tri) * 4;                                     \
+            const float4 a = ldq(S.nodes, base), b = ldq(S.nodes, base + 1), c = ldq(S.nodes, base + 2), e = ldq(S.nodes, base + 3); \
+            const uint32_t fl__ = __float_as_uint(e.w);                                                               \
             int adv__ = 1;                                                                                            \
             float t, u, v;                                                                                            \
-            if (SPC_TRI_PAIRS_LANE) {                                                                                 \
-                /* the triangle's PAIR slot (lbvh.h; behind the node records): both halves of a quad in one step, A first */ \
-                const size_t base = ((size_t)(uint32_t)S.tri_base + (size_t)tri) * 4;                                 \
-                const float4 a = ldq(S.nodes, base), b = ldq(S.nodes, base + 1), c = ldq(S.nodes, base + 2), e = ldq(S.nodes, base + 3); \
-                const uint32_t fl__ = __float_as_uint(e.w);                                                           \
-                h = tri_test<true>(a, b, c, o, d, tmin, best_t, !ANY && (fl__ & 0x80000000u) != 0, t, u, v);                \
-                if (h) { best_t = t; best_tri = tri; best_u = u; best_v = v; }                                        \
-                if ((fl__ & 1u) != 0) {                                                                               \
-                    adv__ = 2;                                                                                        \
-                    if (!(ANY && h)) {                                                                                \
-                        cn.add(C_TRI);                                                                                \
-                        const bool hb__ = tri_test<true>(a, c, e, o, d, tmin, best_t, !ANY && (fl__ & 0x40000000u) != 0, t, u, v); \
-                        if (hb__) { best_t = t; best_tri = tri + 1; best_u = u; best_v = v; }                         \
-                        h = h || hb__;                                                                                \
-                    }                                                                                                 \
+            bool h = tri_test<true>(a, b, c, o, d, tmin, best_t, !ANY && (fl__ & 0x80000000u) != 0, t, u, v);         \
+            if (h) { best_t = t; best_tri = tri; best_u = u; best_v = v; }                                            \
+            if ((fl__ & 1u) != 0) {                                                                                   \
+                adv__ = 2;                                                                                            \
+                if (!(ANY && h)) {                                                                                    \
+                    cn.add(C_TRI);                                                                                    \
+                    const bool hb__ = tri_test<true>(a, c, e, o, d, tmin, best_t, !ANY && (fl__ & 0x40000000u) != 0, t, u, v); \
+                    if (hb__) { best_t = t; best_tri = tri + 1; best_u = u; best_v = v; }                             \
+                    h = h || hb__;                                                                                    \
                 }                                                                                                     \
-            } else {                                                                                                  \
-                const size_t base = (size_t)tri * 4;                                                                  \
-                const float4 a = ldq(S.tris, base), b = ldq(S.tris, base + 1), c = ldq(S.tris, base + 2);             \
-                bool cull = false;                                                                                    \
-                if (!ANY) {                                                                                           \
-                    /* emitter flag lives in quad 3; only fetched for closest-hit rays (single-sided emitters, q16) */ \
-                    cull = (__float_as_uint(ldq(S.tris, base + 3).w) & 0x80000000u) != 0;                             \
-                }                                                                                                     \
-                h = tri_test(a, b, c, o, d, tmin, best_t, cull, t, u, v);                                             \
-                if (h) { best_t = t; best_tri = tri; best_u = u; best_v = v; }                                        \
             }                                                                                                         \
             if (ANY && h) {                                                                                           \
                 node = kTravDone;                                                                                     \
@@ -341,14 +333,6 @@ SPC_DEV bool traverse(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, f3 
     hit.t = best_t; hit.tri = best_tri; hit.u = best_u; hit.v = best_v;
     return best_tri >= 0;
 }
-
-// ---- DPP quad_perm helpers (four consecutive lanes) ---------------------------------------------------------------------
-static constexpr int kQBcast0 = 0x00, kQBcast1 = 0x55, kQBcast2 = 0xAA, kQBcast3 = 0xFF;
-static constexpr int kQRot1 = 0x39, kQRot2 = 0x4E, kQRot3 = 0x93, kQXor1 = 0xB1;   // [1,2,3,0] [2,3,0,1] [3,0,1,2] [1,0,3,2]
-template <int CTRL>
-SPC_DEV uint32_t quad_perm(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true); }
-template <int CTRL>
-SPC_DEV float quad_permf(float v) { return __uint_as_float(quad_perm<CTRL>(__float_as_uint(v))); }
 
 // ---- fan-out tail: the last shadow rays of a wave's pass, each on as many quads as the wave has to spare -----------------
 // A shadow ray asks one question (is ANY triangle in the way), so the order in which its nodes are visited is free: the
@@ -448,22 +432,8 @@ SPC_DEV void fan_tail(const DeviceScene& S, const TravStack<BLOCK, STACK_LDS>& s
                 const float4 rec = ldq(S.nodes_q, (size_t)cur * NODE_QUADS + qr);
                 if (qr == 0u) cn.add(C_NODE);
                 if (COUNT) { cn.add(C_U_NODE_LANES); cn.add(C_U_TAIL_SHADOW); }
-                const float ox = quad_permf<kQBcast0>(rec.w), oy = quad_permf<kQBcast1>(rec.w), oz = quad_permf<kQBcast2>(rec.w);
-                const uint32_t e = quad_perm<kQBcast3>(__float_as_uint(rec.w));
-                const float ax = __uint_as_float((e & 0xffu) << 23) * inv.x, ay = __uint_as_float(((e >> 8) & 0xffu) << 23) * inv.y,
-                            az = __uint_as_float(((e >> 16) & 0xffu) << 23) * inv.z;
-                const float bx = fmaf(ox, inv.x, -ood.x), by = fmaf(oy, inv.y, -ood.y), bz = fmaf(oz, inv.z, -ood.z);
-                const uint32_t pa = __float_as_uint(rec.x), pb = __float_as_uint(rec.y);
-                const float lx = (float)(pa & 255u), ly = (float)((pa >> 8) & 255u), lz = (float)((pa >> 16) & 255u), hx = (float)(pa >> 24),
-                            hy = (float)(pb & 255u), hz = (float)((pb >> 8) & 255u);
-                const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;
-                const float tnx = fmaf(sx ? hx : lx, ax, bx), tfx = fmaf(sx ? lx : hx, ax, bx);
-                const float tny = fmaf(sy ? hy : ly, ay, by), tfy = fmaf(sy ? ly : hy, ay, by);
-                const float tnz = fmaf(sz ? hz : lz, az, bz), tfz = fmaf(sz ? lz : hz, az, bz);
-                const float t0 = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, kEps));
-                const float t1 = fminf(fminf(tfx, tfy), fminf(tfz, tmax));
-                hit = t0 <= t1 * 1.0000004f;
-                key = hit ? ((__float_as_uint(t0) & ~3u) | qr) : NONE;
+                const QuadSlab qs = slab1q(rec, inv, ood, kEps, tmax, qr);
+                hit = qs.hit; key = qs.key;
                 cref = __float_as_uint(rec.z);
             }
             if (COUNT && (int)lane == __ffsll((long long)__ballot(1)) - 1) { cn.add(C_U_NODE_SLOTS, 64); cn.add(C_U_TAIL_SLOTS, 64); }
@@ -529,33 +499,17 @@ SPC_DEV void fan_tail(const DeviceScene& S, const TravStack<BLOCK, STACK_LDS>& s
 static constexpr int POOL_RAYS = 64 * SPCBPT_CONNECTION_N;
 // Compacts the slots of the wave's ray pool that hold a ray (length >= 0) into s_list; returns their number (wave-uniform).  All 64
 // lanes call it after the rays of the iteration have been written (wave-scope fence before and after).
-// LONGEST FIRST (SPC_POOL_BUCKETS > 1): a pass ends when its last ray ends, and the lanes that find the pool empty idle until then --
+// LONGEST FIRST: a pass ends when its last ray ends, and the lanes that find the pool empty idle until then --
 // 37 % of the pass's iterations ran after the pool was dry, at 47 % of the lanes.  The rays are drawn in list order, so the list is
 // written in order of decreasing length class (bounds 2, 1, 1/2 of the wave's mean length: the work of an unoccluded shadow ray
 // grows with the nodes its segment crosses): the long rays start first and the short ones fill the end of the pass, as in
 // longest-processing-time-first scheduling.  Which lane traces which ray, and when, changes; every ray and its answer do not.
-#ifndef SPC_POOL_BUCKETS
-#define SPC_POOL_BUCKETS 4
-#endif
-#ifndef SPC_PROBE_HALVE_LONG
-#define SPC_PROBE_HALVE_LONG 0   // TIMING PROBE (images invalid): the rays of the longest class end at half their length -- what splitting them in two could save at most
-#endif
-SPC_DEV uint32_t pool_ray_list(const float4* s_ray, uint8_t* s_list, float* s_mean = nullptr) {
+SPC_DEV uint32_t pool_ray_list(const float4* s_ray, uint8_t* s_list) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t n = 0u;
     float len[SPCBPT_CONNECTION_N];
 #pragma unroll
     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) len[it] = s_ray[it * 64 + lane].w;
-    if (SPC_POOL_BUCKETS <= 1) {
-#pragma unroll
-        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-            const bool has = len[it] >= 0.0f;
-            const unsigned long long m = __ballot(has);
-            if (has) s_list[n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)(it * 64 + lane);
-            n += (uint32_t)__popcll(m);
-        }
-        return n;
-    }
     // the wave's mean ray length
     float sum = 0.0f;
     uint32_t cnt = 0u;
@@ -565,17 +519,15 @@ SPC_DEV uint32_t pool_ray_list(const float4* s_ray, uint8_t* s_list, float* s_me
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (cnt == 0u) return 0u;
     const float mean = sum / (float)cnt;
-    if (SPC_PROBE_HALVE_LONG && s_mean && lane == 0) *s_mean = mean;
-    // class 0 = longest.  SPC_POOL_BUCKETS = 2: [mean, inf), [0, mean); 4: [2 mean, inf), [mean, 2 mean), [mean / 2, mean), [0, mean / 2)
+    // class 0 = longest: [2 mean, inf), [mean, 2 mean), [mean / 2, mean), [0, mean / 2)
     int cls[SPCBPT_CONNECTION_N];
 #pragma unroll
     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-        if (SPC_POOL_BUCKETS == 2) cls[it] = len[it] >= mean ? 0 : 1;
-        else cls[it] = len[it] >= 2.0f * mean ? 0 : (len[it] >= mean ? 1 : (len[it] >= 0.5f * mean ? 2 : 3));
+        cls[it] = len[it] >= 2.0f * mean ? 0 : (len[it] >= mean ? 1 : (len[it] >= 0.5f * mean ? 2 : 3));
         if (!(len[it] >= 0.0f)) cls[it] = -1;
     }
 #pragma unroll
-    for (int c = 0; c < (SPC_POOL_BUCKETS == 2 ? 2 : 4); c++) {
+    for (int c = 0; c < 4; c++) {
 #pragma unroll
         for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
             const bool has = cls[it] == c;
@@ -603,7 +555,6 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
     st.sp = 0;
     if (own) cn.add(C_CLOSEST);
     own_hit.t = 1e16f; own_hit.tri = -1; own_hit.u = own_hit.v = 0.0f;
-#if SPC_ONE_FETCH
     // ONE gather per iteration, issued one step AHEAD: a lane on an internal node needs its 64-B node record, a lane on a leaf its
     // 64-B triangle record -- the same four loads with another base.  The record of the NEXT step is requested as soon as the step
     // that decides it is done, so the fetch is in flight while the finished lanes store their results and draw new rays (an LDS
@@ -618,7 +569,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
     // same registers from memory: the compiler has to wait for those first -- vmcnt(0) in nearly every iteration.)
 #define SPC_FETCH_STEP__()                                                                                            \
     do {                                                                                                              \
-        const int fn__ = (SPC_ROOT_AHEAD && node == kTravDone) ? 0 : node;                                            \
+        const int fn__ = node == kTravDone ? 0 : node;                                                                \
         if ((uint32_t)fn__ < (uint32_t)n_hot) {                                                                \
             /* one of the hottest nodes (lbvh.cpp numbers them first): the block's LDS copy, no trip through the vector L1 */ \
             const float4* h__ = s_hot + fn__ * 4;                                                                     \
@@ -629,8 +580,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
         R0 = ldq(S.nodes, rb__); R1 = ldq(S.nodes, rb__ + 1); R2 = ldq(S.nodes, rb__ + 2); R3 = ldq(S.nodes, rb__ + 3); \
         }                                                                                                             \
     } while (0)
-    if (SPC_ROOT_AHEAD || node != kTravDone) SPC_FETCH_STEP__();
-#endif
+    SPC_FETCH_STEP__();
     while (true) {
         if (node == kTravDone && !done) {  // acquire the next shadow ray of the pool
             const uint32_t k = atomicAdd(s_next, 1u);
@@ -642,26 +592,15 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
             o = mk3(oq.x, oq.y, oq.z); d = mk3(rq.x, rq.y, rq.z);
             inv = safe_inv(d); ood = o * inv;
             best_t = rq.w - kEps;
-            if (SPC_PROBE_HALVE_LONG && rq.w >= 2.0f * __uint_as_float(s_next[1])) best_t = 0.5f * rq.w;
             node = 0; st.sp = 0;
             cn.add(C_SHADOW);
-#if SPC_ONE_FETCH
-            if (!SPC_ROOT_AHEAD) SPC_FETCH_STEP__();   // the root
-#endif
             }
         }
         const unsigned long long live__ = __ballot(node != kTravDone);
         if (live__ == 0ull) break;
         // The pool is dry (some lane found it empty; the cursor only grows) and at most 16 rays are still in flight: the rest of the
         // pass is the tail that used to run these iterations at a fifth of the lanes.  Hand each ray to FOUR lanes (quad tail below).
-#if SPC_PROBE_DROP_TAIL
-        // TIMING PROBES (images invalid; profiles/r06_experiments.md): what the end of the pass costs -- the upper bound of anything that
-        // would carry its unfinished shadow rays into the next pass.  1: the rays the quad tail would take over are dropped (left
-        // unoccluded) when no closest-hit ray is among them; 2: every shadow ray still in flight once the pool is dry and the
-        // closest-hit rays are done.
-        if (__any(done) && !__any(node != kTravDone && closest) && (SPC_PROBE_DROP_TAIL == 2 || __popcll(live__) <= 16)) break;
-#endif
-        if (SPC_QUAD_TAIL && S.nodes_q && __popcll(live__) <= 16 && __any(done)) { quad_live = live__; break; }
+        if (S.nodes_q && __popcll(live__) <= 16 && __any(done)) { quad_live = live__; break; }
         const bool tail = COUNT && __any(done);   // (counting build) some lane found the pool empty: what follows is the pass's tail
         bool finished = false, occluded = false;
         const bool shallow__ = !__any(node != kTravDone && st.sp + 3 > STACK_LDS);   // no lane near the end of its LDS entries (wave-uniform)
@@ -697,7 +636,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                     /* the slot of a FAN PAIR (lbvh.h: R0 .. R2 = A's corners, R3.xyz = B's third corner, B = (A.P0, A.P2, R3)): this step */ \
                     /* tests both, A first and B against what A left of the interval -- the operations and the order of two steps */ \
                     const uint32_t fl__ = __float_as_uint(R3.w);                                                      \
-                    const bool pair__ = SPC_TRI_PAIRS && (fl__ & 1u) != 0;                                            \
+                    const bool pair__ = (fl__ & 1u) != 0;                                                             \
                     const bool cull = closest && (fl__ & 0x80000000u) != 0;  /* single-sided emitters */              \
                     float t, u, v;                                                                                    \
                     bool h = tri_test<true>(R0, R1, R2, o, d, kEps, best_t, cull, t, u, v);                                 \
@@ -712,8 +651,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                     if (h && !closest) {                                                                              \
                         occluded = true; finished = true; node = kTravDone;                                           \
                     } else {                                                                                          \
-                        /* SPC_PROBE_TRI_PAIRS (timing probe, images invalid): a step answers for two triangles of the leaf */ \
-                        const int adv__ = (pair__ || (SPC_PROBE_TRI_PAIRS && leaf_count >= 2)) ? 2 : 1;               \
+                        const int adv__ = pair__ ? 2 : 1;                                                             \
                         node -= adv__;  /* ~(tri + 1) */                                                              \
                         leaf_count -= adv__;                                                                          \
                         if (leaf_count == 0) { SPC_TRAV_POP_(POP); finished = node == kTravDone; }                    \
@@ -724,9 +662,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
             else SPC_POOL_STEP__(push_far, pop);
 #undef SPC_POOL_STEP__
         }
-#if SPC_ONE_FETCH
-        if ((node != kTravDone || (SPC_ROOT_AHEAD && !done)) && !hold__) SPC_FETCH_STEP__();   // the next step's record: ONE request site after the step, outside its branches
-#endif
+        if ((node != kTravDone || !done) && !hold__) SPC_FETCH_STEP__();   // the next step's record: ONE request site after the step, outside its branches
         if (finished) {
             if (closest) {
                 own_hit.t = best_t; own_hit.tri = best_tri; own_hit.u = best_u; own_hit.v = best_v;
@@ -738,10 +674,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
         }
     }
 #undef SPC_FETCH_STEP__
-    if (SPC_QUAD_TAIL && quad_live != 0ull) {
-#if SPC_PRIO_TAIL >= 0
-        __builtin_amdgcn_s_setprio(SPC_PRIO_TAIL);   // (experiment: the tails at another priority than the lane loop; the caller resets it after the pass)
-#endif
+    if (quad_live != 0ull) {
         // ---- quad tail: the k-th ray still in flight continues on lanes 4 k .. 4 k + 3 -------------------------------------------
         // Lane r of a quad loads record r of the node (one coalesced 64-B line per ray), tests ITS child, and the four entry
         // distances are ranked across the quad: the same keys, the same order, the same pushes as SPC_NODE_STEP -- onto the SAME
@@ -775,31 +708,17 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
         const f3 qinv = safe_inv(qd), qood = qo * qinv;
         lds_u32* const col = st.wave_lds + owner;
         uint32_t* const q_spill = st.spill ? st.spill + ((long long)owner - (long long)lane) * (long long)st.spill_entries : nullptr;
-        bool q_occluded = false, q_done = !has;
+        bool q_occluded = false;
         while (__any(q_node != kTravDone)) {
             // no closest-hit ray left: the shadow rays that remain need no order any more (fan_tail below)
-            if (SPC_FAN_TAIL && S.fan_tail && !__any(q_node != kTravDone && q_closest)) break;
+            if (S.fan_tail && !__any(q_node != kTravDone && q_closest)) break;
             if (q_node != kTravDone) {
                 bool finished = false;
                 if (q_node >= 0) {
                     const float4 rec = ldq(S.nodes_q, (size_t)q_node * NODE_QUADS + qr);
                     if (qr == 0u) cn.add(C_NODE);
                     if (COUNT) { cn.add(C_U_NODE_LANES); cn.add(q_closest ? C_U_TAIL_CLOSEST : C_U_TAIL_SHADOW); if ((int)lane == __ffsll((long long)__ballot(1)) - 1) { cn.add(C_U_NODE_SLOTS, 64); cn.add(C_U_TAIL_SLOTS, 64); } }
-                    const float ox = quad_permf<kQBcast0>(rec.w), oy = quad_permf<kQBcast1>(rec.w), oz = quad_permf<kQBcast2>(rec.w);
-                    const uint32_t e = quad_perm<kQBcast3>(__float_as_uint(rec.w));
-                    const float ax = __uint_as_float((e & 0xffu) << 23) * qinv.x, ay = __uint_as_float(((e >> 8) & 0xffu) << 23) * qinv.y,
-                                az = __uint_as_float(((e >> 16) & 0xffu) << 23) * qinv.z;
-                    const float bx = fmaf(ox, qinv.x, -qood.x), by = fmaf(oy, qinv.y, -qood.y), bz = fmaf(oz, qinv.z, -qood.z);
-                    const uint32_t pa = __float_as_uint(rec.x), pb = __float_as_uint(rec.y);
-                    const float lx = (float)(pa & 255u), ly = (float)((pa >> 8) & 255u), lz = (float)((pa >> 16) & 255u), hx = (float)(pa >> 24),
-                                hy = (float)(pb & 255u), hz = (float)((pb >> 8) & 255u);
-                    const bool sx = qinv.x < 0.0f, sy = qinv.y < 0.0f, sz = qinv.z < 0.0f;
-                    const float tnx = fmaf(sx ? hx : lx, ax, bx), tfx = fmaf(sx ? lx : hx, ax, bx);
-                    const float tny = fmaf(sy ? hy : ly, ay, by), tfy = fmaf(sy ? ly : hy, ay, by);
-                    const float tnz = fmaf(sz ? hz : lz, az, bz), tfz = fmaf(sz ? lz : hz, az, bz);
-                    const float t0 = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, kEps));
-                    const float t1 = fminf(fminf(tfx, tfy), fminf(tfz, q_best));
-                    const uint32_t key = (t0 <= t1 * 1.0000004f) ? ((__float_as_uint(t0) & ~3u) | qr) : 0xffffffffu;
+                    const uint32_t key = slab1q_key(rec, qinv, qood, kEps, q_best, qr);
                     const uint32_t ref = __float_as_uint(rec.z);
                     const uint32_t k1 = quad_perm<kQRot1>(key), k2 = quad_perm<kQRot2>(key), k3 = quad_perm<kQRot3>(key);
                     const bool hit = key != 0xffffffffu;
@@ -820,8 +739,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                         next = mine | quad_perm<kQRot1>(mine) | quad_perm<kQRot2>(mine) | quad_perm<kQRot3>(mine);
                     }
                     if (next == 0xffffffffu) { q_node = kTravDone; finished = true; }
-                    else if (next & 0x80000000u) { q_node = ~(int)((next & 0x7fffffffu) >> 3); q_leaf = (int)(next & 7u); }
-                    else q_node = (int)next;
+                    else SPC_STACK_DECODE(next, q_node, q_leaf);
                 }
                 if (!finished && q_node < 0) {
                     float t = 1e30f, u = 0.0f, v = 0.0f;
@@ -848,15 +766,11 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                         else {
                             q_sp--;
                             const uint32_t w = q_sp < STACK_LDS ? col[q_sp * BLOCK] : stack_pop_slow(q_spill, st.spill_entries, q_sp - STACK_LDS);
-                            if (w & 0x80000000u) { q_node = ~(int)((w & 0x7fffffffu) >> 3); q_leaf = (int)(w & 7u); }
-                            else q_node = (int)w;
+                            SPC_STACK_DECODE(w, q_node, q_leaf);
                         }
                     }
                 }
-                if (finished) {
-                    q_done = true;
-                    if (!q_closest && qr == 0u && q_occluded) s_ray[q_r].w = -1.0f;
-                }
+                if (finished && !q_closest && qr == 0u && q_occluded) s_ray[q_r].w = -1.0f;
             }
         }
         // ---- closest-hit rays of the tail: the winner's record goes back to the owner lane through the owner's stack column, which is
@@ -882,8 +796,7 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                 own_hit.u = __uint_as_float(mine[2 * BLOCK]); own_hit.v = __uint_as_float(mine[3 * BLOCK]);
             }
         }
-        (void)q_done;
-        if (SPC_FAN_TAIL && S.fan_tail && __any(q_node != kTravDone))
+        if (S.fan_tail && __any(q_node != kTravDone))
             fan_tail<COUNT, BLOCK, STACK_LDS>(S, st, q_node != kTravDone, qo, qd, q_best, q_node == kTravDone ? 0xffffffffu : stack_word(q_node, q_leaf > 0 ? q_leaf : 0), q_sp, owner,
                                               q_r, s_ray, list, cn);
     }

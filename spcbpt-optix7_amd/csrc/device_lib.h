@@ -199,7 +199,7 @@ SPC_DEV int mesh_light_pick(const DeviceScene& S, const DLight& L, float u) {   
     do {
         const float4 q0 = *reinterpret_cast<const float4*>(cmf + pos), q1 = *reinterpret_cast<const float4*>(cmf + pos + 4);
         guide_window<false>(q0, q1, pos, c0, padded, u, s);
-        pos += SPC_GUIDE_WINDOW;
+        pos += GUIDE_WINDOW;
     } while (!(s.hi < INFINITY) && pos < padded);
     return min(s.cnt, count - 1);
 }

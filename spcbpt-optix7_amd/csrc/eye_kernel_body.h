@@ -11,10 +11,8 @@
     struct alignas(16) WavePool {
         float4 ray[POOL_RAYS];      // shadow ray it * 64 + lane: direction.xyz, length (< 0: none)
         float4 org[64];             // eye vertex of lane l: position.xyz (= origin of its shadow rays), lastNormalProjection
-#if !SPC_POOL_SLOTS_IN_REGS
         int32_t slot[POOL_RAYS];    // LVC slot of connection it * 64 + lane
         float pmf[POOL_RAYS];       // its resampling pmf (path_count * pmf2 * pmf1)
-#endif
         uint8_t job[POOL_RAYS];     // before the pass: slots that hold a ray; after it: the unoccluded connections, compacted
                                     // (the pass answers a shadow ray in the ray's own slot: an occluded pair's length becomes -1 = no ray)
         uint32_t next;              // pool cursor
@@ -29,15 +27,8 @@
     // wave_in_block through readfirstlane: the per-wave LDS base below is then a wave-uniform value the compiler keeps in an SGPR
     const uint32_t lane = threadIdx.x & 63, wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WavePool* wp = s_pool + wave_in_block;
-#if SPC_POOL_SLOTS_IN_REGS
-    int32_t my_slot[SPCBPT_CONNECTION_N];   // LVC slot of this lane's connection `it` ...
-    float my_pmf[SPCBPT_CONNECTION_N];      // ... and its resampling pmf (path_count * pmf2 * pmf1)
-#pragma unroll
-    for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { my_slot[it] = 0; my_pmf[it] = 1.0f; }
-#else
     int32_t* w_slot = wp->slot;
     float* w_pmf = wp->pmf;
-#endif
     uint8_t* w_job = wp->job;
     uint32_t* w_stack = s_stack + wave_in_block * 64;      // [entry * BLOCK + lane]: free between two traversal passes
     float4* w_ray = wp->ray;
@@ -128,7 +119,7 @@
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // the slots that hold a shadow ray, compacted (w_job is free here: the connect phase below rebuilds it after the pass)
-        const uint32_t n_rays = pool_ray_list(w_ray, w_job, reinterpret_cast<float*>(w_next + 1));
+        const uint32_t n_rays = pool_ray_list(w_ray, w_job);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // the vertex's five small integers cross the pass in two registers (the pass needs every register it can get: the kernel spills)
@@ -141,9 +132,9 @@
         // of what it issues), connect and shading are chains of dependent fetches with little to issue in between -- a wave in the pass
         // goes first when both are ready.  Measured (profiles/r05_experiments.md, section 16): pass 1 / others 0: +1.1 % paths per second;
         // any phase but the pass raised: the light pass that shares the CUs (priority 0 throughout) starves and the step gets longer.
-        if (SPC_PRIO_TRAV != SPC_PRIO_SHADE || SPC_PRIO_TAIL >= 0) __builtin_amdgcn_s_setprio(SPC_PRIO_TRAV);
+        if (SPC_PRIO_TRAV != SPC_PRIO_SHADE) __builtin_amdgcn_s_setprio(SPC_PRIO_TRAV);
         trace_pool(S, st, alive && has_ray, fresh ? ld3(p.eye) : cur.c.pos, w.dir, h, w_org, w_ray, w_next, w_job, n_rays, cn, s_hot, EYE_HOT);
-        if (SPC_PRIO_CONNECT != SPC_PRIO_TRAV || SPC_PRIO_TAIL >= 0) __builtin_amdgcn_s_setprio(SPC_PRIO_CONNECT);
+        if (SPC_PRIO_CONNECT != SPC_PRIO_TRAV) __builtin_amdgcn_s_setprio(SPC_PRIO_CONNECT);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         cur.sub = (int)(ids_a & 1023u); cur.lastZone = (int)((ids_a >> 10) & 1023u); cur.depth = (int)(ids_a >> 20);
@@ -163,9 +154,6 @@
                 if (live) {
                     w_job[n_jobs + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)(it * 64 + lane);
                     my_live |= 1u << it;
-#if SPC_POOL_SLOTS_IN_REGS
-                    w_ray[it * 64 + lane] = make_float4(__int_as_float(my_slot[it]), my_pmf[it], 0.0f, 0.0f);   // (the pass is over: the slot's direction is free)
-#endif
                 }
                 n_jobs += (uint32_t)__popcll(m);
             }
@@ -207,14 +195,8 @@
                     const LightVertex* job_lvc = BATCH ? p.frames[ids >> 26].lvc_sorted : p.lvc_sorted;   // (w_slot holds the vertex's place in the sampler's order)
                     a.c.mat = (int)(col[15 * BLOCK] & 0xffffu); a.lsub = (int)(col[15 * BLOCK] >> 16);
                     LightVertex b;
-#if SPC_POOL_SLOTS_IN_REGS
-                    const float4 sp = w_ray[slot];
-                    const float4* src = reinterpret_cast<const float4*>(job_lvc + __float_as_int(sp.x));
-                    const float job_pmf = sp.y;
-#else
                     const float4* src = reinterpret_cast<const float4*>(job_lvc + w_slot[slot]);
                     const float job_pmf = w_pmf[slot];
-#endif
                     float4* dst = reinterpret_cast<float4*>(&b);
 #pragma unroll
                     for (int q = 0; q < 6; q++) dst[q] = src[q];
@@ -286,55 +268,16 @@
                         f_lvc = D.lvc_sorted; f_subspace = D.subspace; f_cmfs = D.cmfs; f_guide = D.guide; f_path_count = D.sampler_counts[1];
                         f_counts = D.sampler_counts;
                     }
-                    // Three stages, each over all CONNECTION_N connections, so that what does not depend on each other is in flight together:
+                    // Three stages, each over all CONNECTION_N connections:
                     // (1) per connection, in order (the random numbers are one stream, and an empty subspace draws none for its second stage):
-                    //     the light subspace and its record; (2) the bisections of sampleSecondStage side by side -- one round trip per level
-                    //     for the three of them instead of three; (3) the sampled slots, the light vertices' position quads and the rays.
+                    //     the light subspace and its record; (2) sampleSecondStage of each through the guide table, one window at a time;
+                    //     (3) the sampled slots, the light vertices' position quads and the rays.
+                    // (The first stages side by side on a guessed stream, and the second-stage windows in flight together, save round trips and
+                    // LOSE: they cost registers in a kernel that spills -- profiles/r05_experiments.md, sections 4 and 22.)
                     float pmf1_[SPCBPT_CONNECTION_N], pmf2_[SPCBPT_CONNECTION_N], u2_[SPCBPT_CONNECTION_N];
                     int lslot_[SPCBPT_CONNECTION_N], bias_[SPCBPT_CONNECTION_N], size_[SPCBPT_CONNECTION_N];
 #pragma unroll
                     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { pmf1_[it] = 1.0f; pmf2_[it] = 0.0f; u2_[it] = 0.0f; lslot_[it] = -1; bias_[it] = 0; size_[it] = 0; }
-                    // The random numbers of a vertex's connections are ONE stream -- u1, [u2 unless the light subspace drawn with u1 is
-                    // empty], u1, ... -- so connection k's first number is known only when connection k - 1's subspace record has arrived:
-                    // four dependent round trips per connection, twelve per vertex.  An empty subspace is never drawn from a trained
-                    // matrix (its Gamma column is zero) and rarely otherwise, so the numbers are drawn as if none were empty: the
-                    // CONNECTION_N first stages then run side by side on one coarse fetch (sample_first_stage_n: three round trips for all
-                    // of them), the subspace records follow together, and the guess is checked -- a vertex with an empty subspace in
-                    // front of its last connection starts over in the reference's order (the loop below), with the seed as it was.
-                    bool in_order = SPC_JOINT_FIRST_STAGE == 0 || p.uniform_lvc != 0 || p.cmf_gamma2 == nullptr;
-                    if (!in_order) {
-                        uint32_t sd = w.seed;
-                        float u1[SPCBPT_CONNECTION_N], u2[SPCBPT_CONNECTION_N], pm[SPCBPT_CONNECTION_N];
-                        uint32_t after_u1[SPCBPT_CONNECTION_N];
-                        int l[SPCBPT_CONNECTION_N];
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { u1[it] = rnd(sd); after_u1[it] = sd; u2[it] = rnd(sd); }
-#if SPC_GUIDE
-                        int windows[SPCBPT_CONNECTION_N];
-                        sample_first_stage_guided_n<SPCBPT_CONNECTION_N>(p.cmf_gamma2, p.cmf_guide1, cur.sub, u1, l, pm, windows);
-#else
-                        sample_first_stage_n<SPCBPT_CONNECTION_N, SPC_JOINT_FIRST_STAGE == 2>(p.cmf_gamma2, cur.sub, u1, l, pm);
-#endif
-                        DSubspace ss[SPCBPT_CONNECTION_N];
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) ss[it] = f_subspace[l[it]];
-#pragma unroll
-                        for (int it = 0; it + 1 < SPCBPT_CONNECTION_N; it++) in_order = in_order || ss[it].size == 0;
-                        if (!in_order) {
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                pmf1_[it] = pm[it];
-                                if (ss[it].size != 0) { bias_[it] = ss[it].jump_bias; size_[it] = ss[it].size; u2_[it] = u2[it]; }
-#if SPC_GUIDE
-                                if (COUNT) cn.add(C_CMF, CACHE ? 1u + (unsigned)SPC_GUIDE_WINDOW * (unsigned)windows[it] : (unsigned)bisection_probes(l[it], SPCBPT_NUM_SUBSPACE));
-#else
-                                if (COUNT) cn.add(C_CMF, CACHE ? (it == 0 ? 32u : 16u) : (unsigned)bisection_probes(l[it], SPCBPT_NUM_SUBSPACE));
-#endif
-                            }
-                            w.seed = ss[SPCBPT_CONNECTION_N - 1].size != 0 ? sd : after_u1[SPCBPT_CONNECTION_N - 1];
-                        }
-                    }
-                    if (in_order) {
 #pragma unroll
                     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                         if (p.uniform_lvc) {   // the comparator of BASELINE config 5: uniformSample (cuProg.h:283-289), one random number
@@ -346,104 +289,21 @@
                             if (ss.size != 0) { bias_[it] = ss.jump_bias; size_[it] = ss.size; u2_[it] = rnd(w.seed); }
                         }
                     }
-                    }
-#if SPC_GUIDE
                     {   // binary_sample (cuProg.h:245-264) of the three through the guide table (device_lib.h: guide_window); every sampler build
-                        // writes one (capi.hip: set_guide is allocated with the CMF), so there is no bisection beside it in this build
+                        // writes one (capi.hip: set_guide is allocated with the CMF), so there is no bisection beside it
 #include "second_stage_guided.inc.h"
                     }
-#else
-                    {   // binary_sample (cuProg.h:245-264) of the three, level by level
-                        int lo_[SPCBPT_CONNECTION_N], hi_[SPCBPT_CONNECTION_N], mid_[SPCBPT_CONNECTION_N];
-#if SPC_SECOND_STAGE_ARY == 4
-                        // ... as a 4-ary search: the sampler's CMFs are non-decreasing by construction (k_sb_cmf: a normalised prefix sum,
-                        // a zero-weight subspace is uniform), so the bisection's bin is the first k with u < cmf[k], size - 1 if there is
-                        // none -- three probes per level find it in half the dependent round trips (five for 263 entries instead of nine)
-                        (void)mid_;
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { lo_[it] = 0; hi_[it] = size_[it] > 0 ? size_[it] - 1 : 0; }
-                        bool any_open = false;
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) any_open = any_open || hi_[it] > lo_[it];
-                        while (any_open) {
-                            float a_[SPCBPT_CONNECTION_N], b_[SPCBPT_CONNECTION_N], c_[SPCBPT_CONNECTION_N];
-                            int m1_[SPCBPT_CONNECTION_N], m2_[SPCBPT_CONNECTION_N], m3_[SPCBPT_CONNECTION_N];
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                const int n = hi_[it] - lo_[it];
-                                m1_[it] = lo_[it] + (n >> 2); m2_[it] = lo_[it] + (n >> 1); m3_[it] = lo_[it] + ((3 * n) >> 2);
-                                const bool open = n > 0;
-                                a_[it] = open ? f_cmfs[bias_[it] + m1_[it]] : 0.0f;
-                                b_[it] = open ? f_cmfs[bias_[it] + m2_[it]] : 0.0f;
-                                c_[it] = open ? f_cmfs[bias_[it] + m3_[it]] : 0.0f;
-                            }
-                            any_open = false;
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (hi_[it] > lo_[it]) {
-                                    if (COUNT) cn.add(C_CMF, 3);
-                                    const float u = u2_[it];
-                                    if (u < a_[it]) hi_[it] = m1_[it];
-                                    else if (u < b_[it]) { lo_[it] = m1_[it] + 1; hi_[it] = m2_[it]; }
-                                    else if (u < c_[it]) { lo_[it] = m2_[it] + 1; hi_[it] = m3_[it]; }
-                                    else lo_[it] = m3_[it] + 1;
-                                }
-                                any_open = any_open || hi_[it] > lo_[it];
-                            }
-                        }
-#else
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { lo_[it] = 0; hi_[it] = size_[it]; mid_[it] = size_[it] / 2 - 1; }
-                        bool any_open = false;
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) any_open = any_open || hi_[it] - lo_[it] > 1;
-                        while (any_open) {
-                            float v_[SPCBPT_CONNECTION_N];
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) v_[it] = hi_[it] - lo_[it] > 1 ? f_cmfs[bias_[it] + mid_[it]] : 0.0f;
-                            any_open = false;
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (hi_[it] - lo_[it] > 1) {
-                                    cn.add(C_CMF);
-                                    if (u2_[it] < v_[it]) hi_[it] = mid_[it] + 1;
-                                    else lo_[it] = mid_[it] + 1;
-                                    mid_[it] = (lo_[it] + hi_[it]) / 2 - 1;
-                                }
-                                any_open = any_open || hi_[it] - lo_[it] > 1;
-                            }
-                        }
-#endif
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                            if (size_[it] != 0) {
-                                const float* cmf = f_cmfs + bias_[it];
-                                const int k = lo_[it];
-                                pmf2_[it] = k == 0 ? cmf[k] : cmf[k] - cmf[k - 1];
-                                lslot_[it] = bias_[it] + k;   // its record in the sorted cache (what jump[bias + k] names in the cache's own order)
-                            }
-                        }
-                    }
-#endif
 #pragma unroll
                     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                         const float pmf1 = pmf1_[it], pmf2 = pmf2_[it];
                         const int lslot = lslot_[it];
                         float4 rq = make_float4(0.f, 0.f, 0.f, -1.0f);
                         if (lslot >= 0) {
-#if SPC_POOL_SLOTS_IN_REGS
-                            my_slot[it] = lslot;
-#else
                             w_slot[it * 64 + lane] = lslot;
-#endif
                             cn.add(C_CONN);
                             const float4 bq0 = reinterpret_cast<const float4*>(f_lvc + lslot)[0];
                             const float4 bq1 = reinterpret_cast<const float4*>(f_lvc + lslot)[1];
-#if SPC_POOL_SLOTS_IN_REGS
-                            my_pmf[it] = (float)f_path_count * pmf2 * pmf1;
-#else
                             w_pmf[it * 64 + lane] = (float)f_path_count * pmf2 * pmf1;
-#endif
                             // a light vertex that is a DIRECTION of the environment map (only scenes with one pay the flag fetch):
                             // visibilityTest shoots from the eye vertex to eye - 10 r n_b (cuProg.h:489-495)
                             const bool b_dir = ENV && (f_lvc[lslot].pad & SPCBPT_LV_DIRECTION) != 0u;

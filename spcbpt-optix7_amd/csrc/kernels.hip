@@ -21,9 +21,6 @@ namespace spc {
 #ifndef SPC_EYE_BLOCK
 #define SPC_EYE_BLOCK 256
 #endif
-#ifndef SPC_SECOND_STAGE_ARY
-#define SPC_SECOND_STAGE_ARY 2    // 4: sampleSecondStage as a 4-ary search (below)
-#endif
 // Issue priority of a wave by phase (s_setprio, 0 .. 3): see the traversal pass in k_spcbpt
 #ifndef SPC_PRIO_TRAV
 #define SPC_PRIO_TRAV 1
@@ -34,24 +31,9 @@ namespace spc {
 #ifndef SPC_PRIO_SHADE
 #define SPC_PRIO_SHADE 0
 #endif
-#ifndef SPC_JOINT_FIRST_STAGE
-#define SPC_JOINT_FIRST_STAGE 0   // 1 / 2: the first stages of a vertex's connections on one coarse fetch (below: measured, slower)
-#endif
 static constexpr int EYE_BLOCK = SPC_EYE_BLOCK;
-#ifndef SPC_POOL_SLOTS_IN_REGS
-// 1: the LVC slot and the pmf of a lane's three connections cross the traversal pass in the lane's own registers (i.e. in its scratch:
-// six more dwords of parked state) and are handed to the job loop in the xy of the ray slot, whose direction the pass no longer
-// needs -- instead of two 768-B arrays per wave in LDS, which become 96 more hot nodes per block.  Measured (profiles/r05_experiments.md,
-// section 24): the scratch costs +1.4 %, 115 instead of 19 hot nodes give back 0.4 %.
-#define SPC_POOL_SLOTS_IN_REGS 0
-#endif
-#if defined(SPC_EYE_HOT_OVERRIDE)
-static constexpr int EYE_HOT = SPC_EYE_HOT_OVERRIDE;   // (experiments)
-#elif SPC_POOL_SLOTS_IN_REGS
-static constexpr int EYE_HOT = HOT_NODES < 115 || SPC_EYE_BLOCK >= 512 ? HOT_NODES : 115;   // node records [0, EYE_HOT) live in LDS (256 threads: what 40 960 B leave)
-#else
 static constexpr int EYE_HOT = SPC_EYE_BLOCK >= 1024 ? 64 : (SPC_EYE_BLOCK >= 512 ? 38 : 19);   // node records [0, EYE_HOT) live in LDS
-#endif
+// (carrying the pool's slot and pmf arrays in registers to make room for 96 more hot nodes: +0.9 %, profiles/r05_experiments.md, section 24)
 static_assert(EYE_HOT <= HOT_NODES, "the builder numbers HOT_NODES nodes first (layout.h)");
 static_assert(STACK_LDS >= 16, "the pooled connections publish 16 dwords per eye vertex through the traversal-stack LDS");
 #ifndef SPC_EYE_WAVES

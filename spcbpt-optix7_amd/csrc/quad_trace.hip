@@ -26,14 +26,6 @@ static constexpr int QRAYS = QBLOCK / 4;    // rays (quads) in flight per block
 static constexpr int QSTACK = 64;           // stack entries per ray
 static constexpr int QSTRIDE = QSTACK + 1;  // odd stride: the four pushes of a quad and the quads of a wave spread over the banks
 
-// DPP quad_perm controls
-static constexpr int kBcast0 = 0x00, kBcast1 = 0x55, kBcast2 = 0xAA, kBcast3 = 0xFF;
-static constexpr int kRot1 = 0x39, kRot2 = 0x4E, kRot3 = 0x93, kXor1 = 0xB1;   // [1,2,3,0] [2,3,0,1] [3,0,1,2] [1,0,3,2]
-template <int CTRL>
-SPC_DEV uint32_t qperm(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true); }
-template <int CTRL>
-SPC_DEV float qpermf(float v) { return __uint_as_float(qperm<CTRL>(__float_as_uint(v))); }
-
 // node layout of the quad kernels: record r (float4 r of the 64-B node) =
 //   x: qlo.x[r] | qlo.y[r] << 8 | qlo.z[r] << 16 | qhi.x[r] << 24     y: qhi.y[r] | qhi.z[r] << 8
 //   z: stack word of child r (layout.h: internal node index, or leaf ref)   w: r = 0..2: origin.x/y/z, r = 3: scale exponents
@@ -128,24 +120,10 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad(const DeviceScene S, cons
                 // ---- node visit: one 16-B record per lane, the child of this lane
                 const float4 rec = ldq(reinterpret_cast<const float*>(A.nodes_q), (size_t)node * 4 + r);
                 if (STATS && r == 0u) n_node++;
-                const float ox = qpermf<kBcast0>(rec.w), oy = qpermf<kBcast1>(rec.w), oz = qpermf<kBcast2>(rec.w);
-                const uint32_t e = qperm<kBcast3>(__float_as_uint(rec.w));
-                const float ax = __uint_as_float((e & 0xffu) << 23) * inv.x, ay = __uint_as_float(((e >> 8) & 0xffu) << 23) * inv.y,
-                            az = __uint_as_float(((e >> 16) & 0xffu) << 23) * inv.z;
-                const float bx = fmaf(ox, inv.x, -ood.x), by = fmaf(oy, inv.y, -ood.y), bz = fmaf(oz, inv.z, -ood.z);
-                const uint32_t pa = __float_as_uint(rec.x), pb = __float_as_uint(rec.y);
-                const float lx = (float)(pa & 255u), ly = (float)((pa >> 8) & 255u), lz = (float)((pa >> 16) & 255u), hx = (float)(pa >> 24),
-                            hy = (float)(pb & 255u), hz = (float)((pb >> 8) & 255u);
-                const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;
-                const float tnx = fmaf(sx ? hx : lx, ax, bx), tfx = fmaf(sx ? lx : hx, ax, bx);
-                const float tny = fmaf(sy ? hy : ly, ay, by), tfy = fmaf(sy ? ly : hy, ay, by);
-                const float tnz = fmaf(sz ? hz : lz, az, bz), tfz = fmaf(sz ? lz : hz, az, bz);
-                const float t0 = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-                const float t1 = fminf(fminf(tfx, tfy), fminf(tfz, best_t));
-                const uint32_t key = (t0 <= t1 * 1.0000004f) ? ((__float_as_uint(t0) & ~3u) | r) : 0xffffffffu;
+                const uint32_t key = slab1q_key(rec, inv, ood, tmin, best_t, r);
                 const uint32_t ref = __float_as_uint(rec.z);
                 // ---- rank across the quad (keys of hits are distinct: the slot sits in the low bits)
-                const uint32_t k1 = qperm<kRot1>(key), k2 = qperm<kRot2>(key), k3 = qperm<kRot3>(key);
+                const uint32_t k1 = quad_perm<kQRot1>(key), k2 = quad_perm<kQRot2>(key), k3 = quad_perm<kQRot3>(key);
                 const bool hit = key != 0xffffffffu;
                 const int rank = (k1 < key ? 1 : 0) + (k2 < key ? 1 : 0) + (k3 < key ? 1 : 0);
                 const int nh = (hit ? 1 : 0) + (k1 != 0xffffffffu ? 1 : 0) + (k2 != 0xffffffffu ? 1 : 0) + (k3 != 0xffffffffu ? 1 : 0);
@@ -156,11 +134,10 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad(const DeviceScene S, cons
                     if (hit && rank > 0) stack[sp + nh - 1 - rank] = ref;   // farthest deepest, second nearest on top
                     sp += nh - 1;
                     const uint32_t mine = (hit && rank == 0) ? ref : 0u;
-                    next = mine | qperm<kRot1>(mine) | qperm<kRot2>(mine) | qperm<kRot3>(mine);
+                    next = mine | quad_perm<kQRot1>(mine) | quad_perm<kQRot2>(mine) | quad_perm<kQRot3>(mine);
                 }
                 if (next == 0xffffffffu) { node = kTravDone; finished = true; }
-                else if (next & 0x80000000u) { node = ~(int)((next & 0x7fffffffu) >> 3); leaf_count = (int)(next & 7u); }
-                else node = (int)next;
+                else SPC_STACK_DECODE(next, node, leaf_count);
             }
             if (!finished && node < 0) {
                 // ---- leaf: triangle r of the leaf for lane r (an empty slot's leaf has no triangles)
@@ -178,8 +155,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad(const DeviceScene S, cons
                 }
                 if (STATS && r == 0u) n_leaf++;
                 if (h && t < my_t) { my_t = t; my_tri = tri; my_u = u; my_v = v; }   // (t < best_t <= my_t whenever h)
-                float tq = fminf(t, qpermf<kXor1>(t));
-                tq = fminf(tq, qpermf<kRot2>(tq));
+                float tq = fminf(t, quad_permf<kQXor1>(t));
+                tq = fminf(tq, quad_permf<kQRot2>(tq));
                 if (ANY) {
                     if (tq < 1e30f) { occluded = true; node = kTravDone; finished = true; }
                 } else best_t = fminf(best_t, tq);
@@ -187,8 +164,7 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad(const DeviceScene S, cons
                     if (sp == 0) { node = kTravDone; finished = true; }
                     else {
                         const uint32_t w = stack[--sp];
-                        if (w & 0x80000000u) { node = ~(int)((w & 0x7fffffffu) >> 3); leaf_count = (int)(w & 7u); }
-                        else node = (int)w;
+                        SPC_STACK_DECODE(w, node, leaf_count);
                     }
                 }
             }
@@ -198,8 +174,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad(const DeviceScene S, cons
                 } else {
                     // the winner: the lane that holds the quad's nearest hit; the lowest lane on a tie (= the lower triangle index)
                     const uint32_t cand = (my_tri >= 0 && my_t == best_t) ? r : 4u;
-                    uint32_t w = min(cand, qperm<kXor1>(cand));
-                    w = min(w, qperm<kRot2>(w));
+                    uint32_t w = min(cand, quad_perm<kQXor1>(cand));
+                    w = min(w, quad_perm<kQRot2>(w));
                     if (w == 4u) { if (r == 0u) { A.out_t[ray] = best_t; A.out_tri[ray] = -1; A.out_uv[2 * ray] = 0.f; A.out_uv[2 * ray + 1] = 0.f; } }
                     else if (w == r) { A.out_t[ray] = my_t; A.out_tri[ray] = S.tri_orig[my_tri]; A.out_uv[2 * ray] = my_u; A.out_uv[2 * ray + 1] = my_v; }
                 }
@@ -284,8 +260,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad2(const DeviceScene S, con
             if (node >= 0) {
                 const float4 rec = *reinterpret_cast<const float4*>(node_base + ((uint32_t)node * 64u + r * 16u));
                 if (STATS && r == 0u) n_node++;
-                const float ox = qpermf<kBcast0>(rec.w), oy = qpermf<kBcast1>(rec.w), oz = qpermf<kBcast2>(rec.w);
-                const int e = (int)qperm<kBcast3>(__float_as_uint(rec.w));
+                const float ox = quad_permf<kQBcast0>(rec.w), oy = quad_permf<kQBcast1>(rec.w), oz = quad_permf<kQBcast2>(rec.w);
+                const int e = (int)quad_perm<kQBcast3>(__float_as_uint(rec.w));
                 const float ax = ldexpf(inv.x, (int)(signed char)(e & 255)), ay = ldexpf(inv.y, (int)(signed char)((e >> 8) & 255)),
                             az = ldexpf(inv.z, (int)(signed char)((e >> 16) & 255));
                 const float bx = fmaf(ox, inv.x, -ood.x), by = fmaf(oy, inv.y, -ood.y), bz = fmaf(oz, inv.z, -ood.z);
@@ -303,19 +279,18 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad2(const DeviceScene S, con
                 if (nib == 0u) {
                     if (sp == 0) next = 0xffffffffu; else next = stack[--sp];
                 } else {
-                    uint32_t kmin = min(key, qperm<kXor1>(key));
-                    kmin = min(kmin, qperm<kRot2>(kmin));
+                    uint32_t kmin = min(key, quad_perm<kQXor1>(key));
+                    kmin = min(kmin, quad_perm<kQRot2>(kmin));
                     const bool nearest = key == kmin;
                     const uint32_t others = nib & ~(1u << (kmin & 3u));
                     if (hit && !nearest) stack[sp + (int)__popc(others & below)] = ref;
                     sp += (int)__popc(others);
                     uint32_t mine = nearest ? ref : 0u;
-                    mine |= qperm<kXor1>(mine);
-                    next = mine | qperm<kRot2>(mine);
+                    mine |= quad_perm<kQXor1>(mine);
+                    next = mine | quad_perm<kQRot2>(mine);
                 }
                 if (next == 0xffffffffu) { node = kTravDone; finished = true; }
-                else if (next & 0x80000000u) { node = ~(int)((next & 0x7fffffffu) >> 3); leaf_count = (int)(next & 7u); }
-                else node = (int)next;
+                else SPC_STACK_DECODE(next, node, leaf_count);
             }
             if (!finished && node < 0) {
                 float t = 1e30f, u = 0.f, v = 0.f;
@@ -332,8 +307,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad2(const DeviceScene S, con
                 }
                 if (STATS && r == 0u) n_leaf++;
                 if (h && t < my_t) { my_t = t; my_tri = tri; my_u = u; my_v = v; }
-                float tq = fminf(t, qpermf<kXor1>(t));
-                tq = fminf(tq, qpermf<kRot2>(tq));
+                float tq = fminf(t, quad_permf<kQXor1>(t));
+                tq = fminf(tq, quad_permf<kQRot2>(tq));
                 if (ANY) {
                     if (tq < 1e30f) { occluded = true; node = kTravDone; finished = true; }
                 } else best_t = fminf(best_t, tq);
@@ -341,8 +316,7 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad2(const DeviceScene S, con
                     if (sp == 0) { node = kTravDone; finished = true; }
                     else {
                         const uint32_t w = stack[--sp];
-                        if (w & 0x80000000u) { node = ~(int)((w & 0x7fffffffu) >> 3); leaf_count = (int)(w & 7u); }
-                        else node = (int)w;
+                        SPC_STACK_DECODE(w, node, leaf_count);
                     }
                 }
             }
@@ -351,8 +325,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quad2(const DeviceScene S, con
                     if (r == 0u) A.out_visible[ray] = occluded ? 0 : 1;
                 } else {
                     const uint32_t cand = (my_tri >= 0 && my_t == best_t) ? r : 4u;
-                    uint32_t w = min(cand, qperm<kXor1>(cand));
-                    w = min(w, qperm<kRot2>(w));
+                    uint32_t w = min(cand, quad_perm<kQXor1>(cand));
+                    w = min(w, quad_perm<kQRot2>(w));
                     if (w == 4u) { if (r == 0u) { A.out_t[ray] = best_t; A.out_tri[ray] = -1; A.out_uv[2 * ray] = 0.f; A.out_uv[2 * ray + 1] = 0.f; } }
                     else if (w == r) { A.out_t[ray] = my_t; A.out_tri[ray] = S.tri_orig[my_tri]; A.out_uv[2 * ray] = my_u; A.out_uv[2 * ray + 1] = my_v; }
                 }
@@ -430,24 +404,9 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quadk(const DeviceScene S, con
             bool finished = false;
             if (node[k] != kTravDone && node[k] >= 0) {
                 if (STATS && r == 0u) n_node++;
-                const float ox = qpermf<kBcast0>(rec[k].w), oy = qpermf<kBcast1>(rec[k].w), oz = qpermf<kBcast2>(rec[k].w);
-                const uint32_t e = qperm<kBcast3>(__float_as_uint(rec[k].w));
-                const f3 iv = inv[k], od = ood[k];
-                const float ax = __uint_as_float((e & 0xffu) << 23) * iv.x, ay = __uint_as_float(((e >> 8) & 0xffu) << 23) * iv.y,
-                            az = __uint_as_float(((e >> 16) & 0xffu) << 23) * iv.z;
-                const float bx = fmaf(ox, iv.x, -od.x), by = fmaf(oy, iv.y, -od.y), bz = fmaf(oz, iv.z, -od.z);
-                const uint32_t pa = __float_as_uint(rec[k].x), pb = __float_as_uint(rec[k].y);
-                const float lx = (float)(pa & 255u), ly = (float)((pa >> 8) & 255u), lz = (float)((pa >> 16) & 255u), hx = (float)(pa >> 24),
-                            hy = (float)(pb & 255u), hz = (float)((pb >> 8) & 255u);
-                const bool sx = iv.x < 0.0f, sy = iv.y < 0.0f, sz = iv.z < 0.0f;
-                const float tnx = fmaf(sx ? hx : lx, ax, bx), tfx = fmaf(sx ? lx : hx, ax, bx);
-                const float tny = fmaf(sy ? hy : ly, ay, by), tfy = fmaf(sy ? ly : hy, ay, by);
-                const float tnz = fmaf(sz ? hz : lz, az, bz), tfz = fmaf(sz ? lz : hz, az, bz);
-                const float t0 = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin[k]));
-                const float t1 = fminf(fminf(tfx, tfy), fminf(tfz, best_t[k]));
-                const uint32_t key = (t0 <= t1 * 1.0000004f) ? ((__float_as_uint(t0) & ~3u) | r) : 0xffffffffu;
+                const uint32_t key = slab1q_key(rec[k], inv[k], ood[k], tmin[k], best_t[k], r);
                 const uint32_t ref = __float_as_uint(rec[k].z);
-                const uint32_t k1 = qperm<kRot1>(key), k2 = qperm<kRot2>(key), k3 = qperm<kRot3>(key);
+                const uint32_t k1 = quad_perm<kQRot1>(key), k2 = quad_perm<kQRot2>(key), k3 = quad_perm<kQRot3>(key);
                 const bool hit = key != 0xffffffffu;
                 const int rank = (k1 < key ? 1 : 0) + (k2 < key ? 1 : 0) + (k3 < key ? 1 : 0);
                 const int nh = (hit ? 1 : 0) + (k1 != 0xffffffffu ? 1 : 0) + (k2 != 0xffffffffu ? 1 : 0) + (k3 != 0xffffffffu ? 1 : 0);
@@ -458,11 +417,10 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quadk(const DeviceScene S, con
                     if (hit && rank > 0) stack[sp[k] + nh - 1 - rank] = ref;
                     sp[k] += nh - 1;
                     const uint32_t mine = (hit && rank == 0) ? ref : 0u;
-                    next = mine | qperm<kRot1>(mine) | qperm<kRot2>(mine) | qperm<kRot3>(mine);
+                    next = mine | quad_perm<kQRot1>(mine) | quad_perm<kQRot2>(mine) | quad_perm<kQRot3>(mine);
                 }
                 if (next == 0xffffffffu) { node[k] = kTravDone; finished = true; }
-                else if (next & 0x80000000u) { node[k] = ~(int)((next & 0x7fffffffu) >> 3); leafc[k] = (int)(next & 7u); }
-                else node[k] = (int)next;
+                else SPC_STACK_DECODE(next, node[k], leafc[k]);
             }
             if (!finished && node[k] < 0) {
                 float t = 1e30f, u = 0.f, v = 0.f;
@@ -480,8 +438,8 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quadk(const DeviceScene S, con
                 }
                 if (STATS && r == 0u) n_leaf++;
                 if (h && t < my_t[k]) { my_t[k] = t; my_tri[k] = tri; my_u[k] = u; my_v[k] = v; }
-                float tq = fminf(t, qpermf<kXor1>(t));
-                tq = fminf(tq, qpermf<kRot2>(tq));
+                float tq = fminf(t, quad_permf<kQXor1>(t));
+                tq = fminf(tq, quad_permf<kQRot2>(tq));
                 bool occluded = false;
                 if (ANY) {
                     if (tq < 1e30f) { occluded = true; node[k] = kTravDone; finished = true; }
@@ -490,16 +448,15 @@ __global__ __launch_bounds__(QBLOCK) void k_trace_quadk(const DeviceScene S, con
                     if (sp[k] == 0) { node[k] = kTravDone; finished = true; }
                     else {
                         const uint32_t w = stack[--sp[k]];
-                        if (w & 0x80000000u) { node[k] = ~(int)((w & 0x7fffffffu) >> 3); leafc[k] = (int)(w & 7u); }
-                        else node[k] = (int)w;
+                        SPC_STACK_DECODE(w, node[k], leafc[k]);
                     }
                 }
                 if (ANY && finished && r == 0u) A.out_visible[ray[k]] = occluded ? 0 : 1;
             } else if (ANY && finished && r == 0u) A.out_visible[ray[k]] = 1;   // the stack ran empty on a node visit: nothing hit
             if (!ANY && finished) {
                 const uint32_t cand = (my_tri[k] >= 0 && my_t[k] == best_t[k]) ? r : 4u;
-                uint32_t w = min(cand, qperm<kXor1>(cand));
-                w = min(w, qperm<kRot2>(w));
+                uint32_t w = min(cand, quad_perm<kQXor1>(cand));
+                w = min(w, quad_perm<kQRot2>(w));
                 const int rk = ray[k];
                 if (w == 4u) { if (r == 0u) { A.out_t[rk] = best_t[k]; A.out_tri[rk] = -1; A.out_uv[2 * rk] = 0.f; A.out_uv[2 * rk + 1] = 0.f; } }
                 else if (w == r) { A.out_t[rk] = my_t[k]; A.out_tri[rk] = S.tri_orig[my_tri[k]]; A.out_uv[2 * rk] = my_u[k]; A.out_uv[2 * rk + 1] = my_v[k]; }

@@ -1,4 +1,4 @@
-// The guided second-stage draw of the eye megakernel (eye_kernel_body.h, SPC_GUIDE 1), a TEXT FRAGMENT like eye_kernel_body.h itself:
+// The guided second-stage draw of the eye megakernel (eye_kernel_body.h), a TEXT FRAGMENT like eye_kernel_body.h itself:
 // included inside a block, once by the megakernel and once by the per-function harness (unit.hip: SPCBPT_UNIT_STAGE2_GUIDED), so that
 // what the tests draw through is the product's code and not a restatement of it.  binary_sample (cuProg.h:245-264) of the
 // CONNECTION_N connections through the guide table (dev_sampling.h: guide_window).
@@ -14,9 +14,6 @@
 #pragma unroll
                         for (int it = 0; it < SPCBPT_CONNECTION_N; it++)
                             g_[it] = size_[it] > 0 ? f_guide[bias_[it] + min((int)(u2_[it] * (float)size_[it]), size_[it] - 1)] : 0u;
-#ifndef SPC_GUIDE_SIDE_BY_SIDE
-#define SPC_GUIDE_SIDE_BY_SIDE 0   // 1: the windows of the three connections in flight together (24 registers of CMF values: spills, measured)
-#endif
 #pragma unroll
                         for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                             const int c0 = max((int)g_[it] - 1, 0);
@@ -25,44 +22,19 @@
                             open_[it] = size_[it] > 0;
                             if (COUNT && CACHE && open_[it]) cn.add(C_CMF);   // (the guide entry; the reference-order form charges the bisection's probes below)
                         }
-#if SPC_GUIDE_SIDE_BY_SIDE
-                        bool any_open = false;
-#pragma unroll
-                        for (int it = 0; it < SPCBPT_CONNECTION_N; it++) any_open = any_open || open_[it];
-                        while (any_open) {
-                            float4 a_[SPCBPT_CONNECTION_N], b_[SPCBPT_CONNECTION_N];
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (open_[it]) {
-                                    a_[it] = *reinterpret_cast<const float4*>(f_cmfs + pos_[it]);
-                                    b_[it] = *reinterpret_cast<const float4*>(f_cmfs + pos_[it] + 4);
-                                }
-                            }
-                            any_open = false;
-#pragma unroll
-                            for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
-                                if (open_[it]) {
-                                    if (COUNT && CACHE) cn.add(C_CMF, 8);
-                                    guide_window(a_[it], b_[it], pos_[it], first_[it], bias_[it] + size_[it], u2_[it], s_[it]);
-                                    pos_[it] += 8;
-                                    open_[it] = !(s_[it].hi < INFINITY) && pos_[it] < bias_[it] + size_[it];
-                                }
-                                any_open = any_open || open_[it];
-                            }
-                        }
-#else
+                        // one connection's windows after the other: the three in flight together hold 24 registers of CMF values and spill
+                        // (+18 % against one window at a time: profiles/r05_experiments.md, section 22)
 #pragma unroll
                         for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                             while (open_[it]) {
                                 const float4 a = *reinterpret_cast<const float4*>(f_cmfs + pos_[it]);
-                                const float4 b = SPC_GUIDE_WINDOW == 8 ? *reinterpret_cast<const float4*>(f_cmfs + pos_[it] + 4) : a;
-                                if (COUNT && CACHE) cn.add(C_CMF, SPC_GUIDE_WINDOW);
+                                const float4 b = *reinterpret_cast<const float4*>(f_cmfs + pos_[it] + 4);
+                                if (COUNT && CACHE) cn.add(C_CMF, GUIDE_WINDOW);
                                 guide_window(a, b, pos_[it], first_[it], bias_[it] + size_[it], u2_[it], s_[it]);
-                                pos_[it] += SPC_GUIDE_WINDOW;
+                                pos_[it] += GUIDE_WINDOW;
                                 open_[it] = !(s_[it].hi < INFINITY) && pos_[it] < bias_[it] + size_[it];
                             }
                         }
-#endif
 #pragma unroll
                         for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                             if (size_[it] != 0) {

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
     case SPCBPT_UNIT_STAGE1: {
         uint32_t s1 = r[1], s2 = r[1];
         float pmf1 = 0.0f, pmf2 = 0.0f;
-        const int l1 = sample_first_stage(p, (int)r[0], s1, pmf1, cn);   // what the kernels run: counting passes on a monotone matrix
+        const int l1 = sample_first_stage(p, (int)r[0], s1, pmf1, cn);   // what the kernels run: the guided search on a monotone matrix
         const int l2 = binary_sample(p.cmf_gamma + (size_t)r[0] * SPCBPT_NUM_SUBSPACE, SPCBPT_NUM_SUBSPACE, s2, pmf2, cn);   // the reference's bisection
         o[0] = (uint32_t)l1; stf(o + 1, pmf1); o[2] = s1; o[3] = (uint32_t)l2; stf(o + 4, pmf2); o[5] = s2;
         break;

@@ -1,8 +1,20 @@
 """developer: per-kernel comparison of the gfx950 code in two sets of object files (sources moved between translation units: the split of
-kernels.hip in round 6).  usage: python3 tools/codegen_diff_symbols.py before.o [before2.o ...] -- after.o [after2.o ...]
-Every symbol of the 'before' set must exist in the 'after' set with the same instruction stream (addresses and branch targets aside)."""
+kernels.hip in round 6).  usage: python3 tools/codegen_diff_symbols.py [--ignore-registers] before.o [before2.o ...] -- after.o [after2.o ...]
+Every symbol of the 'before' set must exist in the 'after' set with the same instruction stream (addresses and branch targets aside).
+--ignore-registers: register operands count by their class and width only (v12 = v13, s[2:3] = s[8:9] = vcc, a4 = a5) -- the same
+instructions in the same order, whatever the allocator named the values (a statement moved into a function: the compiler may number
+its registers differently and emit the same code otherwise).  exec, m0 and scc stay themselves."""
 import os, re, shutil, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
+IGNORE_REGS = "--ignore-registers" in sys.argv
+if IGNORE_REGS: sys.argv.remove("--ignore-registers")
+def reg_classes(l):
+    op, _, args = l.partition(" ")
+    args = re.sub(r"\b([vsa])\[(\d+):(\d+)\]", lambda m: f"{m.group(1)}[x{int(m.group(3)) - int(m.group(2)) + 1}]", args)
+    args = re.sub(r"\b([vsa])\d+\b", r"\1", args)
+    args = re.sub(r"\bvcc_(lo|hi)\b", "s", args)
+    args = re.sub(r"\bvcc\b", "s[x2]", args)
+    return op + " " + args
 def symbols(objs):
     out = {}
     for o in objs:
@@ -20,7 +32,7 @@ def symbols(objs):
                 l = re.sub(r"//.*", "", l).strip()
                 l = re.sub(r"<[^>]*>", "<>", l)            # branch targets by symbol + offset
                 l = re.sub(r"\b(s_getpc|s_add_u32|s_addc_u32)\b.*", r"\1 ...", l)   # pc-relative address arithmetic
-                out[cur].append(l)
+                out[cur].append(reg_classes(l) if IGNORE_REGS else l)
         for k in out:   # trailing padding belongs to the object's layout, not to the function
             while out[k] and out[k][-1].split()[0] in ("s_code_end", "s_nop"): out[k].pop()
         shutil.rmtree(d)
