@@ -418,6 +418,62 @@ int spcbpt_clear_accum(spcbpt_ctx* ctx);
  * wait for launches queued behind that merge -- a frame being traced ahead (spcbpt_launch_deferred), light passes ahead. */
 int spcbpt_read_film(spcbpt_ctx* ctx, float* accum_rgba_out, uint8_t* frame_rgba8_out);
 
+/* First-hit feature buffers (no reference counterpart): what the primary ray of "pt" sees first, the guides an image-space
+ * denoiser takes.  The ray is the film's: subframe 0 goes through the pixel centre, subframe k > 0 takes the jitter the film's
+ * sample of that subframe took, so features and film share one pixel footprint.  The sample of a subframe:
+ *   first hit               albedo.rgb                                   albedo.w (coverage)  normal.xyz                 depth (normal.w)
+ *   surface                 base colour (texture: bilinear, wrap,        1                    geometric normal, turned   hit distance
+ *                           pow 2.2 -- what the BSDF is evaluated with)                       against the ray
+ *   emitter, front side     (1, 1, 1)                                    1                    the light's normal         hit distance
+ *   emitter, back side      as a miss (path rays see emitters from the front only)
+ *   miss (sky or nothing)   (1, 1, 1)                                    0                    (0, 0, 0)                  0
+ * Two float4-per-pixel device buffers in the film's row order (row 0 = bottom of the view) hold the running means
+ * lerp(prev, sample, 1 / (subframe + 1)) of these values as they stand (subframe 0 overwrites): coverage is albedo.w, the normal
+ * is the un-normalised mean, depth the mean with zeros for misses; a miss carries albedo 1 so that radiance / albedo needs no
+ * branch.  The rows are spcbpt_launch's 8-row bands; rows outside them are left alone.  The buffers are allocated (zeroed) at the
+ * first feature launch after spcbpt_resize: a context that never asks for features keeps its footprint.  Needs film and camera,
+ * and no deferred frame outstanding (else SPCBPT_ERR_STATE).  Asynchronous, ordered with the film merges like the merge of a
+ * "pt" launch; the film is not touched, event counters are not charged, the kernel-time span is "features". */
+int spcbpt_launch_features(spcbpt_ctx* ctx, uint32_t subframe, int row_begin, int row_end, int row_step);
+/* Host copies of the two buffers (either may be NULL); waits like spcbpt_read_accum.  SPCBPT_ERR_STATE if no feature launch has
+ * been made since the last spcbpt_resize. */
+int spcbpt_read_features(spcbpt_ctx* ctx, float* albedo_rgba, float* normal_depth_rgba);
+
+/* Edge-avoiding a-trous wavelet denoiser (Dammertz et al. 2010) on the demodulated film, guided by the feature buffers.  With
+ *   c_0(p) = accum(p).rgb / max(albedo(p).rgb, 1e-3) per channel,   n(p) = normal_depth(p).xyz,   X(p) = d_c(p) normal_depth(p).w
+ *   (d_c: the normalised ray direction through the centre of pixel p),   L(c) = 0.3 r + 0.6 g + 0.1 b,
+ * iteration i = 0 .. iterations - 1 with step s = 2^i runs over the taps q = p + s (a, b), a, b in -2 .. 2, inside the image:
+ *   w(p, q) = k[a] k[b] exp(- |c_i(q) - c_i(p)|^2 / ((sigma_c 2^-i)^2 (1e-2 + (L(c_i(p)) + L(c_i(q))) / 2)^2)
+ *                           - |n(q) - n(p)|^2 / sigma_n^2  -  |X(q) - X(p)|^2 / (sigma_x s)^2),     k = (1, 4, 6, 4, 1) / 16
+ *   c_{i+1}(p) = sum_q w c_i(q) / sum_q w
+ * and denoised(p).rgb = c_last(p) max(albedo(p).rgb, 1e-3), w = 1.  Smooth weights only: no threshold, no division by a guide.
+ * iterations must be in 1 .. 8 (SPCBPT_ERR_INVALID_ARG); a sigma <= 0 selects its default: SPCBPT_DENOISE_SIGMA_C,
+ * SPCBPT_DENOISE_SIGMA_N, and for sigma_x (a length in scene units) SPCBPT_DENOISE_SIGMA_X_FRACTION of the diagonal of the
+ * scene's bounding box: (4, 1, 0.03), the triple with the lowest RMSE of a 4-frame Cornell box on the grid {1, 2, 4} x
+ * {0.25, 0.5, 1} x {0.01, 0.03, 0.1} (tools/denoise_grid.py). */
+typedef struct spcbpt_denoise_params {
+    int32_t iterations;
+    float sigma_c, sigma_n, sigma_x;
+} spcbpt_denoise_params;
+#define SPCBPT_DENOISE_SIGMA_C 4.0f
+#define SPCBPT_DENOISE_SIGMA_N 1.0f
+#define SPCBPT_DENOISE_SIGMA_X_FRACTION 0.03f
+int spcbpt_denoise_params_struct_size(void);   /* sizeof(spcbpt_denoise_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+/* Denoises the film as of every merge queued so far into a float4 buffer and an RGBA8 frame (the film's tone map) of its own;
+ * accum and frame are not touched.  Needs a film, a feature launch since the last spcbpt_resize and no deferred frame
+ * outstanding (else SPCBPT_ERR_STATE, with text).  Asynchronous; the kernel-time span is "denoise". */
+int spcbpt_denoise(spcbpt_ctx* ctx, const spcbpt_denoise_params* params);
+/* Waits for it and copies the result (either pointer may be NULL).  SPCBPT_ERR_STATE if nothing was denoised since the last resize. */
+int spcbpt_read_denoised(spcbpt_ctx* ctx, float* rgba, uint8_t* rgba8);
+/* The same filter on caller buffers on the host: float4-per-pixel accum, albedo and normal_depth as the read-backs give them, the
+ * camera of spcbpt_set_camera (eye is accepted for symmetry: X enters through differences only).  No context and no GPU needed:
+ * the per-pixel function the kernels run, float32, no contraction.  Without a scene the default of sigma_x is
+ * SPCBPT_DENOISE_SIGMA_X_FRACTION of the bounding-box diagonal of the covered pixels' X.  The inputs are not written.
+ * SPCBPT_ERR_INVALID_ARG for a NULL pointer, an empty image or iterations outside 1 .. 8. */
+int spcbpt_denoise_host(const float* accum_rgba, const float* albedo_rgba, const float* normal_depth_rgba,
+                        const float eye[3], const float U[3], const float V[3], const float W[3],
+                        int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
+
 int spcbpt_get_counters(spcbpt_ctx* ctx, spcbpt_counters* out);
 int spcbpt_reset_counters(spcbpt_ctx* ctx);
 /* Developer aid (no reference counterpart): wave-clock totals the counting build of the "SPCBPT_eye" megakernel spent in

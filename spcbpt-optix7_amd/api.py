@@ -49,6 +49,10 @@ class MeshLight(C.Structure):   # spcbpt_mesh_light
     _fields_ = [("material", C.c_int32), ("emission", C.c_float * 3), ("n_patches", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):   # spcbpt_denoise_params
+    _fields_ = [("iterations", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_x", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("texcoords", C.c_void_p), ("n_vertices", C.c_int32),
                 ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("n_triangles", C.c_int32),
@@ -329,6 +333,24 @@ def camera_splat(eye, U, V, W, width, height, point):
     return dx.value, dy.value, px.value, py.value, we.value
 
 
+def denoise_host(accum, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_c=0.0, sigma_n=0.0, sigma_x=0.0):
+    """spcbpt_denoise_host: the a-trous denoiser of Renderer.denoise on (h, w, 4) float32 arrays as read_accum / read_features give
+    them, seen through the camera (eye, U, V, W).  Host code in float32 -- the per-pixel function the kernels run; no GPU needed.
+    A sigma <= 0 takes its default.  Returns the denoised (h, w, 4) image; the inputs are not written."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (accum, albedo, normal_depth)]
+    h, w = a[0].shape[:2]
+    if any(v.shape != (h, w, 4) for v in a):
+        raise SpcbptError("denoise_host: accum, albedo and normal_depth must be (h, w, 4) arrays of one size")
+    cam = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W)]
+    out = np.zeros((h, w, 4), dtype=np.float32)
+    p = DenoiseParams(int(iterations), float(sigma_c), float(sigma_n), float(sigma_x))
+    rc = lib.spcbpt_denoise_host(_fp(a[0]), _fp(a[1]), _fp(a[2]), *[_fp(v) for v in cam], w, h, C.byref(p), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"denoise_host failed ({rc})")
+    return out
+
+
 def single_leaf_tree(label=0):
     t = np.zeros(1, dtype=TREE_NODE_DTYPE)
     t[0]["leaf"] = 1
@@ -592,6 +614,12 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_trace_closest": [vp, vp, i32, vp, vp, vp],
         "spcbpt_trace_any": [vp, vp, i32, vp],
         "spcbpt_camera_splat": [f32p, f32p, f32p, f32p, i32, i32, f32p, f32p, f32p, C.POINTER(i32), C.POINTER(i32), f32p],
+        "spcbpt_launch_features": [vp, u32, i32, i32, i32],
+        "spcbpt_read_features": [vp, vp, vp],
+        "spcbpt_denoise": [vp, C.POINTER(DenoiseParams)],
+        "spcbpt_denoise_params_struct_size": [],
+        "spcbpt_read_denoised": [vp, vp, vp],
+        "spcbpt_denoise_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
         "spcbpt_preprocess": [vp, i32, i32, i32],
         "spcbpt_set_pretrace": [vp, i32, i32],
         "spcbpt_train_records_count": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -653,6 +681,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench",
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
+    "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_preprocess", "spcbpt_get_subspace", "spcbpt_scene_info", "spcbpt_set_pretrace", "spcbpt_train_records_count",
     "spcbpt_train_records_read", "spcbpt_train_records_import", "spcbpt_train_records_clear", "spcbpt_preprocess_stage",
     "spcbpt_get_gamma", "spcbpt_gltf_load", "spcbpt_scene_file_load", "spcbpt_scene_file_desc", "spcbpt_scene_file_camera",
@@ -753,6 +782,18 @@ class Renderer:
         r0, r1, rs = rows if rows is not None else (0, self.height, 1)
         self._chk(self.lib.spcbpt_launch(self.h, name.encode(), frame, r0, r1, rs), f"launch({name})")
 
+    def launch_features(self, subframe: int, rows=None):
+        """spcbpt_launch_features: the first hit of the film's primary ray of `subframe` (albedo + coverage, geometric normal + depth)
+        merged into the feature buffers as a running mean over the subframes; rows as in launch()."""
+        r0, r1, rs = rows if rows is not None else (0, self.height, 1)
+        self._chk(self.lib.spcbpt_launch_features(self.h, int(subframe), r0, r1, rs), "launch_features")
+
+    def denoise(self, iterations=5, sigma_c=0.0, sigma_n=0.0, sigma_x=0.0):
+        """spcbpt_denoise: the edge-avoiding a-trous filter on the film divided by the first-hit albedo, guided by the feature buffers
+        (launch_features first).  A sigma <= 0 takes its default; sigma_x is a length in scene units.  The film is not touched."""
+        p = DenoiseParams(int(iterations), float(sigma_c), float(sigma_n), float(sigma_x))
+        self._chk(self.lib.spcbpt_denoise(self.h, C.byref(p)), "denoise")
+
     def launch_light_batch(self, first_frame, n):
         """The light passes of launch frames first_frame .. first_frame + n - 1 as one persistent launch (spcbpt_launch_light_batch)."""
         self._chk(self.lib.spcbpt_launch_light_batch(self.h, first_frame, n), "launch_light_batch")
@@ -842,6 +883,22 @@ class Renderer:
         out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self._chk(self.lib.spcbpt_read_frame(self.h, out.ctypes.data), "read_frame")
         return out
+
+    def read_features(self):
+        """(albedo, normal_depth): (h, w, 4) float32 each -- base colour + coverage, normal + depth (spcbpt_read_features)."""
+        self.image_size()
+        a = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        n = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_features(self.h, a.ctypes.data, n.ctypes.data), "read_features")
+        return a, n
+
+    def read_denoised(self):
+        """(rgba float32, rgba8): the result of the last denoise() and its tone-mapped frame (spcbpt_read_denoised)."""
+        self.image_size()
+        d = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        f = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._chk(self.lib.spcbpt_read_denoised(self.h, d.ctypes.data, f.ctypes.data), "read_denoised")
+        return d, f
 
     def clear_accum(self):
         self._chk(self.lib.spcbpt_clear_accum(self.h), "clear_accum")

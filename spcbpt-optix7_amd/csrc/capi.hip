@@ -369,6 +369,7 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     c->deferred.active = false;   // a deferred frame of the old size is dropped with its buffer
     dev_free(c->d_accum); dev_free(c->d_frame);
+    c->free_features();           // feature buffers and denoiser planes of the old size: re-allocated on demand
     HIP_TRY(c, dev_alloc(&c->d_accum, (size_t)w * h * 4));
     HIP_TRY(c, dev_alloc(&c->d_frame, (size_t)w * h));
     for (int s = 0; s < Context::kMaxRender; s++)

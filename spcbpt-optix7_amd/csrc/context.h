@@ -255,6 +255,17 @@ struct Context {
     size_t splat_px[kMaxRender] = {};   // pixels d_splat[k] holds
     int launch_splat(uint32_t frame, int r0, int r1, int rs);
     int finish_frame();
+    // First-hit feature buffers and the denoiser's planes (ctx_features.hip): float4 per pixel each, allocated at the first feature
+    // launch / the first denoise after a resize (spcbpt_resize frees them), so a context that asks for neither keeps its footprint.
+    float *d_feat_albedo = nullptr, *d_feat_normal_depth = nullptr;   // running means of (base colour, coverage) / (normal, depth)
+    float *d_dn_position = nullptr, *d_dn_ping = nullptr, *d_dn_pong = nullptr, *d_denoised = nullptr;
+    uint32_t* d_denoised_frame = nullptr;                             // RGBA8: the film's tone map of d_denoised
+    bool have_features = false, have_denoised = false;                // ... since the last resize
+    int chain_begin();   // the next render stream, behind the last link of the film-merge chain
+    int chain_end();     // ... and this launch as the chain's last link
+    int launch_features(uint32_t subframe, int r0, int r1, int rs);
+    int denoise(const spcbpt_denoise_params& p);
+    void free_features();
     // preprocess.hip
     Preprocessor* pre = nullptr;
     spcbpt_pretrace_path* d_pre_paths = nullptr;

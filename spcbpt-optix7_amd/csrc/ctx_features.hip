@@ -1,0 +1,144 @@
+// Context: the first-hit feature pass (kernels_features.hip) and the a-trous denoiser that reads it (kernels_denoise.hip)
+// (part of the C ABI library: see capi_common.h for the map of its translation units)
+#include "capi_common.h"
+#include "dev_features.h"
+#include "kernels_denoise.h"
+#include "kernels_features.h"
+
+using namespace spc;
+
+namespace spc {
+
+// Both passes are links of the film-merge chain (finish_frame): they take the next render stream, wait for the last link queued and
+// leave ev_merge behind for the next one.  So the running means of consecutive feature launches are applied in launch order, a
+// denoise sees every merge queued before it, and no later merge rewrites the film under it -- the order a "pt" launch's merge has.
+int Context::chain_begin() {
+    rk = (rk + 1) % n_render;
+    rstream = rstreams[rk];
+    if (last_merge_k >= 0 && last_merge_k != rk && rstreams[last_merge_k] != rstream) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_merge[last_merge_k], 0));
+    return 0;
+}
+int Context::chain_end() {
+    HIP_TRY(this, hipEventRecord(ev_merge[rk], rstream));
+    ev_merge_set[rk] = true;
+    last_merge_k = rk;
+    return 0;
+}
+
+void Context::free_features() {
+    dev_free(d_feat_albedo); dev_free(d_feat_normal_depth);
+    dev_free(d_dn_position); dev_free(d_dn_ping); dev_free(d_dn_pong); dev_free(d_denoised); dev_free(d_denoised_frame);
+    have_features = have_denoised = false;
+}
+
+// spcbpt_launch_features: the film is not touched, no event counter is charged; the kernel-time span is "features".
+int Context::launch_features(uint32_t subframe, int r0, int r1, int rs) {
+    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
+    if (!d_accum) { error = "launch_features before spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (!have_camera) { error = "launch_features before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
+    if (rs < 1) rs = 1;
+    if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
+    if (int rc = chain_begin()) return rc;
+    // the buffers: allocated (and zeroed, for the rows a banded launch leaves alone) at the first feature launch after a resize, so
+    // that a context that never asks for features keeps its footprint (spcbpt_resize has freed those of the old size)
+    const size_t px = (size_t)kp.width * kp.height;
+    if (!d_feat_albedo) {
+        HIP_TRY(this, dev_alloc(&d_feat_albedo, px * 4));
+        HIP_TRY(this, dev_alloc(&d_feat_normal_depth, px * 4));
+        HIP_TRY(this, hipMemsetAsync(d_feat_albedo, 0, px * 16, rstream));
+        HIP_TRY(this, hipMemsetAsync(d_feat_normal_depth, 0, px * 16, rstream));
+    }
+    FeatureParams fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.scene = kp.scene;
+    memcpy(fp.eye, kp.eye, 12); memcpy(fp.U, kp.U, 12); memcpy(fp.V, kp.V, 12); memcpy(fp.W, kp.W, 12);
+    fp.width = kp.width; fp.height = kp.height; fp.subframe = subframe;
+    fp.row_begin = r0; fp.row_end = std::min(r1, (int)kp.height); fp.row_step = rs;
+    fp.albedo = d_feat_albedo; fp.normal_depth = d_feat_normal_depth;
+    int rc = ensure_spill((size_t)feature_thread_count(fp), true);
+    if (rc) return rc;
+    fp.spill = kp.spill; fp.spill_entries = kp.spill_entries; fp.diag = kp.diag;
+    time_begin("features", rstream);
+    spc::launch_features(fp, rstream);
+    time_end();
+    HIP_TRY(this, hipGetLastError());
+    have_features = true;
+    return chain_end();
+}
+
+// spcbpt_denoise: demodulate -> `iterations` a-trous passes between two planes -> remodulate + tone map, as one "denoise" span.
+int Context::denoise(const spcbpt_denoise_params& dp) {
+    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
+    if (!d_accum) { error = "denoise before spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (!have_features) { error = "denoise needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (dp.iterations < 1 || dp.iterations > kDenoiseMaxIterations) { error = "denoise: iterations must be in 1..8"; return SPCBPT_ERR_INVALID_ARG; }
+    if (!(dp.sigma_c == dp.sigma_c) || !(dp.sigma_n == dp.sigma_n) || !(dp.sigma_x == dp.sigma_x)) { error = "denoise: a sigma is not a number"; return SPCBPT_ERR_INVALID_ARG; }
+    const float ext[3] = {bbox_hi[0] - bbox_lo[0], bbox_hi[1] - bbox_lo[1], bbox_hi[2] - bbox_lo[2]};
+    const float diag = sqrtf(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]);
+    const float sigma_c = dp.sigma_c > 0.0f ? dp.sigma_c : SPCBPT_DENOISE_SIGMA_C;
+    const float sigma_n = dp.sigma_n > 0.0f ? dp.sigma_n : SPCBPT_DENOISE_SIGMA_N;
+    const float sigma_x = dp.sigma_x > 0.0f ? dp.sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
+    if (int rc = chain_begin()) return rc;
+    const size_t px = (size_t)kp.width * kp.height;
+    if (!d_denoised) {
+        HIP_TRY(this, dev_alloc(&d_dn_position, px * 4));
+        HIP_TRY(this, dev_alloc(&d_dn_ping, px * 4));
+        HIP_TRY(this, dev_alloc(&d_dn_pong, px * 4));
+        HIP_TRY(this, dev_alloc(&d_denoised_frame, px));
+        HIP_TRY(this, dev_alloc(&d_denoised, px * 4));
+    }
+    DenoiseParams q;
+    memset(&q, 0, sizeof(q));
+    memcpy(q.U, kp.U, 12); memcpy(q.V, kp.V, 12); memcpy(q.W, kp.W, 12);
+    q.width = kp.width; q.height = kp.height;
+    q.accum = d_accum; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
+    q.position = d_dn_position; q.ping = d_dn_ping; q.pong = d_dn_pong; q.denoised = d_denoised; q.frame = d_denoised_frame;
+    time_begin("denoise", rstream);
+    launch_demodulate(q, rstream);
+    for (int i = 0; i < dp.iterations; i++) launch_atrous(q, atrous_step(i, sigma_c, sigma_n, sigma_x), (i & 1) == 0, rstream);
+    launch_remodulate(q, (dp.iterations & 1) != 0, rstream);
+    time_end();
+    HIP_TRY(this, hipGetLastError());
+    have_denoised = true;
+    return chain_end();
+}
+
+}  // namespace spc
+
+extern "C" {
+
+int spcbpt_launch_features(spcbpt_ctx* c, uint32_t subframe, int r0, int r1, int rs) {
+    CTX_CHECK(c);
+    return c->launch_features(subframe, r0, r1, rs);
+}
+
+int spcbpt_read_features(spcbpt_ctx* c, float* albedo_rgba, float* normal_depth_rgba) {
+    CTX_CHECK(c);
+    if (!c->have_features) { c->error = "read_features: no feature launch since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (c->sync_all()) return SPCBPT_ERR_HIP;
+    if (int rc = c->check_diag()) return rc;
+    const size_t bytes = (size_t)c->kp.width * c->kp.height * 16;
+    if (albedo_rgba) HIP_TRY(c, hipMemcpy(albedo_rgba, c->d_feat_albedo, bytes, hipMemcpyDeviceToHost));
+    if (normal_depth_rgba) HIP_TRY(c, hipMemcpy(normal_depth_rgba, c->d_feat_normal_depth, bytes, hipMemcpyDeviceToHost));
+    return SPCBPT_OK;
+}
+
+int spcbpt_denoise(spcbpt_ctx* c, const spcbpt_denoise_params* p) {
+    CTX_CHECK(c);
+    if (!p) { c->error = "null params"; return SPCBPT_ERR_INVALID_ARG; }
+    return c->denoise(*p);
+}
+int spcbpt_denoise_params_struct_size(void) { return (int)sizeof(spcbpt_denoise_params); }
+
+int spcbpt_read_denoised(spcbpt_ctx* c, float* rgba, uint8_t* rgba8) {
+    CTX_CHECK(c);
+    if (!c->have_denoised) { c->error = "read_denoised: no spcbpt_denoise since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (c->sync_all()) return SPCBPT_ERR_HIP;
+    if (int rc = c->check_diag()) return rc;
+    const size_t px = (size_t)c->kp.width * c->kp.height;
+    if (rgba) HIP_TRY(c, hipMemcpy(rgba, c->d_denoised, px * 16, hipMemcpyDeviceToHost));
+    if (rgba8) HIP_TRY(c, hipMemcpy(rgba8, c->d_denoised_frame, px * 4, hipMemcpyDeviceToHost));
+    return SPCBPT_OK;
+}
+
+}  // extern "C"

@@ -466,6 +466,7 @@ Context::~Context() {
         if (ev_merge[s]) (void)hipEventDestroy(ev_merge[s]);
         dev_free(d_result[s]); dev_free(d_spill_rs[s]); dev_free(d_splat[s]);
     }
+    free_features();
     if (cstream) (void)hipStreamDestroy(cstream);
     if (stream) (void)hipStreamDestroy(stream);
     for (int s = 0; s < kMaxSets; s++) {

@@ -5,7 +5,10 @@
 // --emissive: the emissive materials of a glTF file light the scene as mesh lights (spcbpt_create_lit); with them a file needs no quad.
 // --alg lt: light tracing (the light-vertex cache splatted onto the film): a light pass and a sampler build per frame over the minimal
 // tuple, no preprocessing; its Mpaths/s line counts the light paths only.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]
+// --denoise: a first-hit feature launch beside every frame and one a-trous denoise (spcbpt_denoise, default parameters) after the last;
+// writes <out>_denoised.pfm / .ppm next to the usual files.  --features: writes the feature buffers as <out>_albedo.pfm,
+// <out>_normal.pfm and <out>_depth.pfm (depth in all three channels).
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--features] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -22,15 +25,36 @@ static void die(spcbpt_ctx* c, const char* what, int rc) {
 }
 #define CHECK(c, call) do { int rc__ = (call); if (rc__) die(c, #call, rc__); } while (0)
 
+// PFM: bottom row first, which is exactly the accum_buffer orientation; channels c0, c1, c2 of a float4 image
+static void write_pfm(const std::string& path, const std::vector<float>& rgba, int width, int height, int c0 = 0, int c1 = 1, int c2 = 2) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
+    fprintf(f, "PF\n%d %d\n-1.0\n", width, height);
+    for (size_t i = 0; i < (size_t)width * height; i++) {
+        const float px[3] = {rgba[4 * i + c0], rgba[4 * i + c1], rgba[4 * i + c2]};
+        fwrite(px, 4, 3, f);
+    }
+    fclose(f);
+}
+// PPM: top row first
+static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8, int width, int height) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
+    fprintf(f, "P6\n%d %d\n255\n", width, height);
+    for (int y = height - 1; y >= 0; y--)
+        for (int x = 0; x < width; x++) fwrite(&rgba8[4 * ((size_t)y * width + x)], 1, 3, f);
+    fclose(f);
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--features] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
     int env_mode = 0;
-    bool minimal = false, emissive = false;
+    bool minimal = false, emissive = false, denoise = false, features = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -40,6 +64,8 @@ int main(int argc, char** argv) {
         else if (a == "--minimal") minimal = true;
         else if (a == "--env-mode" && i + 1 < argc) env_mode = atoi(argv[++i]);
         else if (a == "--emissive") emissive = true;
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--features") features = true;
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -102,6 +128,11 @@ int main(int argc, char** argv) {
             CHECK(ctx, spcbpt_build_sampler(ctx));
         }
         CHECK(ctx, spcbpt_launch(ctx, alg.c_str(), (uint32_t)f, 0, height, 1));  // launchSubframe (609-635)
+        if (denoise || features) CHECK(ctx, spcbpt_launch_features(ctx, (uint32_t)f, 0, height, 1));   // the same subframe's primary rays
+    }
+    if (denoise) {
+        const spcbpt_denoise_params dp = {5, 0.0f, 0.0f, 0.0f};   // the defaults of include/spcbpt.h
+        CHECK(ctx, spcbpt_denoise(ctx, &dp));
     }
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
@@ -112,20 +143,23 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> frame((size_t)width * height * 4);
     CHECK(ctx, spcbpt_read_accum(ctx, accum.data()));
     CHECK(ctx, spcbpt_read_frame(ctx, frame.data()));
-    {  // PFM: bottom row first, which is exactly the accum_buffer orientation
-        FILE* f = fopen((out + ".pfm").c_str(), "wb");
-        fprintf(f, "PF\n%d %d\n-1.0\n", width, height);
-        for (size_t i = 0; i < (size_t)width * height; i++) fwrite(&accum[4 * i], 4, 3, f);
-        fclose(f);
-    }
-    {  // PPM: top row first
-        FILE* f = fopen((out + ".ppm").c_str(), "wb");
-        fprintf(f, "P6\n%d %d\n255\n", width, height);
-        for (int y = height - 1; y >= 0; y--)
-            for (int x = 0; x < width; x++) fwrite(&frame[4 * ((size_t)y * width + x)], 1, 3, f);
-        fclose(f);
-    }
+    write_pfm(out + ".pfm", accum, width, height);
+    write_ppm(out + ".ppm", frame, width, height);
     printf("wrote %s.pfm and %s.ppm\n", out.c_str(), out.c_str());
+    if (denoise) {
+        CHECK(ctx, spcbpt_read_denoised(ctx, accum.data(), frame.data()));
+        write_pfm(out + "_denoised.pfm", accum, width, height);
+        write_ppm(out + "_denoised.ppm", frame, width, height);
+        printf("wrote %s_denoised.pfm and %s_denoised.ppm\n", out.c_str(), out.c_str());
+    }
+    if (features) {
+        std::vector<float> normal_depth((size_t)width * height * 4);
+        CHECK(ctx, spcbpt_read_features(ctx, accum.data(), normal_depth.data()));
+        write_pfm(out + "_albedo.pfm", accum, width, height);
+        write_pfm(out + "_normal.pfm", normal_depth, width, height);
+        write_pfm(out + "_depth.pfm", normal_depth, width, height, 3, 3, 3);
+        printf("wrote %s_albedo.pfm, %s_normal.pfm and %s_depth.pfm\n", out.c_str(), out.c_str(), out.c_str());
+    }
     spcbpt_destroy(ctx);
     spcbpt_scene_file_free(sf);
     return 0;
