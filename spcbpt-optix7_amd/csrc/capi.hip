@@ -95,17 +95,13 @@ static int create_context(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* 
             if (ov && std::string(ov) == "0") c->rstreams[s] = c->stream;
             else if (use_prio) CREATE_TRY(hipStreamCreateWithPriority(&c->rstreams[s], hipStreamNonBlocking, prio_least));
             else CREATE_TRY(hipStreamCreateWithFlags(&c->rstreams[s], hipStreamNonBlocking));
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_merge[s], hipEventDisableTiming));
+            CREATE_TRY(hipEventCreateWithFlags(&c->ev_merge[s].ev, hipEventDisableTiming));
         }
         c->rstream = c->rstreams[0];
+        c->lanes[0].stream = c->stream;
         for (int s = 0; s < c->n_sets; s++) {
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_sampler[s], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_render[s], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_light[s], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_set_stream[s], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&c->ev_exch[s], hipEventDisableTiming));
-            c->set_bound[s] = -1;
-            c->set_count_host[s] = -1;
+            CacheSet& S = c->sets[s];
+            for (Event* e : {&S.sampler, &S.render, &S.light, &S.on_stream, &S.exch}) CREATE_TRY(hipEventCreateWithFlags(&e->ev, hipEventDisableTiming));
         }
         CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_import_counts), (size_t)Context::kMaxSets * 2 * sizeof(int)));
         CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_light_counts), (size_t)Context::kMaxSets * 2 * sizeof(int)));
@@ -223,16 +219,16 @@ static int create_context(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* 
     // right behind the node records: the pooled traversal step fetches "the record of its next step" through one base pointer
     // (dev_traversal.h: SPC_FETCH_STEP__).  The per-triangle records (corners + UVs + material: what the tails, the one-ray-per-lane
     // loop and the shading read) live in an allocation of their own.
-    CREATE_TRY(dev_alloc(&c->d_nodes, bvh.nodes.size() + bvh.pairs.size()));
-    CREATE_TRY(dev_alloc(&c->d_tris, bvh.tris.size()));
+    CREATE_TRY(c->d_nodes.reserve(bvh.nodes.size() + bvh.pairs.size()));
+    CREATE_TRY(c->d_tris.reserve(bvh.tris.size()));
     if (getenv("SPCBPT_NO_TRI_PAIRS")) {   // test switch: every slot a single triangle (the same device code, one test per step): films must not change
         for (size_t i = 0; i < bvh.pairs.size() / 16; i++) { uint32_t fl; memcpy(&fl, &bvh.pairs[i * 16 + 15], 4); fl &= 0x80000000u; memcpy(&bvh.pairs[i * 16 + 15], &fl, 4); }
         bvh.n_paired = 0;
     }
     CREATE_TRY(hipMemcpy(c->d_nodes + bvh.nodes.size(), bvh.pairs.data(), bvh.pairs.size() * 4, hipMemcpyHostToDevice));
     c->n_paired = bvh.n_paired;
-    CREATE_TRY(dev_alloc(&c->d_tri_orig, bvh.tri_orig.size()));
-    CREATE_TRY(dev_alloc(&c->d_mats, mats.size()));
+    CREATE_TRY(c->d_tri_orig.reserve(bvh.tri_orig.size()));
+    CREATE_TRY(c->d_mats.reserve(mats.size()));
     CREATE_TRY(hipMemcpy(c->d_nodes, bvh.nodes.data(), bvh.nodes.size() * 4, hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_tris, bvh.tris.data(), bvh.tris.size() * 4, hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_tri_orig, bvh.tri_orig.data(), bvh.tri_orig.size() * 4, hipMemcpyHostToDevice));
@@ -251,41 +247,41 @@ static int create_context(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* 
         CREATE_TRY(hipMemcpy(d, t.rgba, (size_t)t.width * t.height * 4, hipMemcpyHostToDevice));
         texs.push_back(DTexture{d, t.width, t.height});
     }
-    CREATE_TRY(dev_alloc(&c->d_tex, texs.size()));
+    CREATE_TRY(c->d_tex.reserve(texs.size()));
     if (!texs.empty()) CREATE_TRY(hipMemcpy(c->d_tex, texs.data(), texs.size() * sizeof(DTexture), hipMemcpyHostToDevice));
-    CREATE_TRY(dev_alloc(&c->d_set_counts_all, (size_t)2 * Context::kMaxSets + 2));   // + a spare pair (probe_lvc_capacity)
+    CREATE_TRY(c->d_set_counts_all.reserve((size_t)2 * Context::kMaxSets + 2));   // + a spare pair (probe_lvc_capacity)
     CREATE_TRY(hipMemset(c->d_set_counts_all, 0, (2 * Context::kMaxSets + 2) * sizeof(int)));
     for (int s = 0; s < c->n_sets; s++) {
-        CREATE_TRY(dev_alloc(&c->set_subspace[s], (size_t)SPCBPT_NUM_SUBSPACE));
-        c->set_counts[s] = c->d_set_counts_all + 2 * s;
+        CREATE_TRY(c->sets[s].subspace.reserve((size_t)SPCBPT_NUM_SUBSPACE));
+        c->sets[s].counts = c->d_set_counts_all + 2 * s;
     }
-    c->select_set(0);
     {
         hipDeviceProp_t prop;
         CREATE_TRY(hipGetDeviceProperties(&prop, device));
         c->num_cus = prop.multiProcessorCount;
     }
-    CREATE_TRY(dev_alloc(&c->d_work_counter, (size_t)Context::kMaxRender + 2));   // tile queues of the render streams + core queues of the two light lanes
-    CREATE_TRY(dev_alloc(&c->d_diag, (size_t)4));
+    CREATE_TRY(c->d_work_counter.reserve((size_t)Context::kMaxRender + 2));   // tile queues of the render streams + core queues of the two light lanes
+    for (int lane = 0; lane < 2; lane++) c->lanes[lane].work_counter = c->d_work_counter + Context::kMaxRender + lane;
+    CREATE_TRY(c->d_diag.reserve((size_t)4));
     CREATE_TRY(hipMemset(c->d_diag, 0, 4 * sizeof(uint32_t)));
     if (const char* e = getenv("SPCBPT_DEBUG_SPILL_ENTRIES")) c->spill_entries_debug = std::max(0, atoi(e));
-    CREATE_TRY(dev_alloc(&c->d_counters, (size_t)C_COUNT));
+    CREATE_TRY(c->d_counters.reserve((size_t)C_COUNT));
     CREATE_TRY(hipMemset(c->d_counters, 0, C_COUNT * sizeof(unsigned long long)));
     memset(&c->kp, 0, sizeof(c->kp));
     if (c->upload_lights()) { g_create_error = c->error; delete c; return SPCBPT_ERR_HIP; }
     c->kp.scene.nodes = c->d_nodes; c->kp.scene.tris = c->d_tris; c->kp.scene.tri_base = c->n_nodes; c->kp.scene.tri_orig = c->d_tri_orig; c->kp.scene.mats = c->d_mats;
     c->kp.scene.lights = c->d_lights; c->kp.scene.tex = c->d_tex; c->kp.scene.n_lights = c->n_lights; c->kp.scene.n_mats = c->n_mats;
     // the same nodes, one record per child: the quad tail of the pooled traversal pass (device_lib.h) and the traversal A/B harness
-    CREATE_TRY(dev_alloc(&c->d_nodes_q, (size_t)c->n_nodes * 16));
+    CREATE_TRY(c->d_nodes_q.reserve((size_t)c->n_nodes * 16));
     launch_repack_nodes_quad(c->d_nodes, c->d_nodes_q, c->n_nodes, c->stream);
     CREATE_TRY(hipGetLastError());
     CREATE_TRY(hipStreamSynchronize(c->stream));
-    c->kp.scene.nodes_q = getenv("SPCBPT_NO_QUAD_TAIL") ? nullptr : c->d_nodes_q;
+    c->kp.scene.nodes_q = getenv("SPCBPT_NO_QUAD_TAIL") ? nullptr : c->d_nodes_q.p;
     c->kp.scene.fan_tail = getenv("SPCBPT_NO_FAN_TAIL") ? 0 : 1;
     c->kp.scene.general = 0;   // no environment map yet; a flagged material (Pbr::brdf) selects the general kernels as well
     for (const DMaterial& m : mats) if (m.brdf) c->kp.scene.general = 1;
     if (n_ml > 0) c->kp.scene.general = 1;   // the mesh branch of eye_emitter_hit lives in the general forms only (eye_walk.h)
-    c->kp.sampler_counts = c->d_sampler_counts;
+    c->kp.sampler_counts = c->sets[0].counts;
     c->kp.diag = c->d_diag;
     c->kp.row_step = 1;
     CREATE_TRY(hipDeviceSynchronize());   // the uploads above went through the default stream; the context's streams do not wait for it
@@ -368,15 +364,14 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     if (w < 1 || h < 1 || (long long)w * h > (1ll << 28)) { c->error = "bad image size"; return SPCBPT_ERR_INVALID_ARG; }
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     c->deferred.active = false;   // a deferred frame of the old size is dropped with its buffer
-    dev_free(c->d_accum); dev_free(c->d_frame);
+    c->d_accum.release(); c->d_frame.release();
     c->free_features();           // feature buffers and denoiser planes of the old size: re-allocated on demand
-    HIP_TRY(c, dev_alloc(&c->d_accum, (size_t)w * h * 4));
-    HIP_TRY(c, dev_alloc(&c->d_frame, (size_t)w * h));
-    for (int s = 0; s < Context::kMaxRender; s++)
-        for (int k = 0; k < kMaxBatchFrames; k++) { dev_free(c->d_result_b[s][k]); c->d_result_b[s][k] = nullptr; }   // re-allocated at the new size on demand
+    HIP_TRY(c, c->d_accum.reserve((size_t)w * h * 4));
+    HIP_TRY(c, c->d_frame.reserve((size_t)w * h));
+    for (auto& slots : c->d_result_b) for (auto& r : slots) r.release();   // re-allocated at the new size on demand
     for (int s = 0; s < c->n_render; s++) {
-        dev_free(c->d_result[s]);
-        HIP_TRY(c, dev_alloc(&c->d_result[s], (size_t)w * h * 4));
+        c->d_result[s].release();
+        HIP_TRY(c, c->d_result[s].reserve((size_t)w * h * 4));
     }
     HIP_TRY(c, hipMemsetAsync(c->d_accum, 0, (size_t)w * h * 16, c->rstream));
     HIP_TRY(c, hipMemsetAsync(c->d_frame, 0, (size_t)w * h * 4, c->rstream));

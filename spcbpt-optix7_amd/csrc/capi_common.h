@@ -35,22 +35,6 @@ void spc_viewers_forget_context(spcbpt_ctx* ctx);   // viewer.cpp: called by spc
         }                                                                                        \
     } while (0)
 
-namespace spc {
-
-template <class T>
-static hipError_t dev_alloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T));
-}
-template <class T>
-static void dev_free(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-}  // namespace spc
-
 struct spcbpt_ctx : public spc::Context {};
 
 #define CTX_CHECK(c)                                  \

@@ -18,13 +18,13 @@ int spcbpt_image_size(spcbpt_ctx* c, int* w, int* h) { CTX_CHECK(c); if (w) *w =
 int spcbpt_lvc_read(spcbpt_ctx* c, spcbpt_light_vertex* out, int capacity, int* count) {
     CTX_CHECK(c);
     if (!count) return SPCBPT_ERR_INVALID_ARG;
-    if (!c->d_lvc) { c->error = "no LVC"; return SPCBPT_ERR_STATE; }
+    if (!c->sets[c->lset].lvc) { c->error = "no LVC"; return SPCBPT_ERR_STATE; }
     int rc = c->fetch_counts();
     if (rc) return rc;
     *count = c->lvc_count;
     if (!out) return SPCBPT_OK;
     if (capacity < c->lvc_count) { c->error = "lvc_read: buffer too small"; return SPCBPT_ERR_CAPACITY; }
-    HIP_TRY(c, hipMemcpy(out, c->d_lvc, (size_t)c->lvc_count * sizeof(LightVertex), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out, c->sets[c->lset].lvc, (size_t)c->lvc_count * sizeof(LightVertex), hipMemcpyDeviceToHost));
     return SPCBPT_OK;
 }
 
@@ -34,18 +34,18 @@ int spcbpt_sampler_read(spcbpt_ctx* c, spcbpt_subspace* sub, float* cmfs, int32_
     if (!sub || !vc || !pc) return SPCBPT_ERR_INVALID_ARG;
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     std::vector<DSubspace> h(SPCBPT_NUM_SUBSPACE);
-    const int e = c->eset;   // the set of the last sampler build (not necessarily the latest light pass's)
-    HIP_TRY(c, hipMemcpy(h.data(), c->set_subspace[e], h.size() * sizeof(DSubspace), hipMemcpyDeviceToHost));
+    const CacheSet& S = c->sets[c->eset];   // the set of the last sampler build (not necessarily the latest light pass's)
+    HIP_TRY(c, hipMemcpy(h.data(), S.subspace, h.size() * sizeof(DSubspace), hipMemcpyDeviceToHost));
     for (int i = 0; i < SPCBPT_NUM_SUBSPACE; i++) {
         sub[i].jump_bias = h[i].jump_bias; sub[i].id = i; sub[i].size = h[i].size; sub[i].sum_pmf = h[i].sum_pmf; sub[i].q = 0;
     }
     int hc[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(hc, c->set_counts[e], sizeof(hc), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hc, S.counts, sizeof(hc), hipMemcpyDeviceToHost));
     *vc = hc[0]; *pc = hc[1];
     if (cmfs && jump) {
         if (capacity < hc[0]) { c->error = "sampler_read: buffer too small"; return SPCBPT_ERR_CAPACITY; }
-        HIP_TRY(c, hipMemcpy(cmfs, c->set_cmfs[e], (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(jump, c->set_vals2[e], (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(cmfs, S.cmfs, (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(jump, S.jump, (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
     }
     return SPCBPT_OK;
 }
@@ -72,7 +72,7 @@ int spcbpt_read_film(spcbpt_ctx* c, float* accum_out, uint8_t* frame_out) {
     CTX_CHECK(c);
     if (!c->d_accum || !c->d_frame) { c->error = "no film (spcbpt_resize first)"; return SPCBPT_ERR_STATE; }
     if (!c->cstream) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
-    if (c->last_merge_k >= 0 && c->ev_merge_set[c->last_merge_k]) HIP_TRY(c, hipStreamWaitEvent(c->cstream, c->ev_merge[c->last_merge_k], 0));
+    if (c->last_merge_k >= 0) HIP_TRY(c, c->ev_merge[c->last_merge_k].wait_on(c->cstream));
     const size_t px = (size_t)c->kp.width * c->kp.height;
     if (accum_out) HIP_TRY(c, hipMemcpyAsync(accum_out, c->d_accum, px * 16, hipMemcpyDeviceToHost, c->cstream));
     if (frame_out) HIP_TRY(c, hipMemcpyAsync(frame_out, c->d_frame, px * 4, hipMemcpyDeviceToHost, c->cstream));
@@ -92,9 +92,9 @@ int spcbpt_debug_read_sampling_tables(spcbpt_ctx* c, uint32_t* guide2, int capac
     if (guide2) {
         if (!c->have_sampler) { c->error = "no sampler built"; return SPCBPT_ERR_STATE; }
         int hc[2] = {0, 0};
-        HIP_TRY(c, hipMemcpy(hc, c->set_counts[c->eset], sizeof(hc), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(hc, c->sets[c->eset].counts, sizeof(hc), hipMemcpyDeviceToHost));
         if (capacity2 < hc[0]) { c->error = "debug_read_sampling_tables: buffer too small"; return SPCBPT_ERR_CAPACITY; }
-        HIP_TRY(c, hipMemcpy(guide2, c->set_guide[c->eset], (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(guide2, c->sets[c->eset].guide, (size_t)hc[0] * 4, hipMemcpyDeviceToHost));
     }
     if ((guide1 || gamma_q) && !c->d_guide1) { c->error = "no subspace tuple installed"; return SPCBPT_ERR_STATE; }
     if (guide1) HIP_TRY(c, hipMemcpy(guide1, c->d_guide1, (size_t)SPCBPT_NUM_SUBSPACE * CMF_GUIDE1 * sizeof(uint16_t), hipMemcpyDeviceToHost));
@@ -198,7 +198,7 @@ int spcbpt_lvc_import_wait(spcbpt_ctx* c) {
 // a later light pass may already be running ahead.  With nothing pending it waits for the light stream.
 int spcbpt_sync_light(spcbpt_ctx* c) {
     CTX_CHECK(c);
-    if (!c->pending.empty()) HIP_TRY(c, hipEventSynchronize(c->ev_light[c->pending.front()]));
+    if (!c->pending.empty()) HIP_TRY(c, hipEventSynchronize(c->sets[c->pending.front()].light.ev));
     else HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SPCBPT_OK;
 }
@@ -209,9 +209,8 @@ int spcbpt_sync(spcbpt_ctx* c) { CTX_CHECK(c); if (c->sync_all()) return SPCBPT_
 int spcbpt_debug_spill_arm(spcbpt_ctx* c) {
     CTX_CHECK(c);
     if (c->sync_all()) return SPCBPT_ERR_HIP;
-    if (c->d_spill) HIP_TRY(c, hipMemset(c->d_spill, 0xff, c->spill_capacity * 4));
-    if (c->b_spill) HIP_TRY(c, hipMemset(c->b_spill, 0xff, c->b_spill_capacity * 4));
-    for (int k = 0; k < Context::kMaxRender; k++) if (c->d_spill_rs[k]) HIP_TRY(c, hipMemset(c->d_spill_rs[k], 0xff, c->spill_rs_capacity[k] * 4));
+    for (const LightLane& L : c->lanes) if (L.spill) HIP_TRY(c, hipMemset(L.spill, 0xff, L.spill.cap * 4));
+    for (const auto& sp : c->d_spill_rs) if (sp) HIP_TRY(c, hipMemset(sp, 0xff, sp.cap * 4));
     HIP_TRY(c, hipDeviceSynchronize());
     return SPCBPT_OK;
 }
@@ -221,15 +220,15 @@ int spcbpt_debug_spill_count(spcbpt_ctx* c, uint64_t* written, int* entries_per_
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     uint64_t n = 0;
     std::vector<uint32_t> h;
-    auto scan = [&](const uint32_t* d, size_t words) -> int {
-        if (!d || !words) return 0;
-        h.resize(words);
-        HIP_TRY(c, hipMemcpy(h.data(), d, words * 4, hipMemcpyDeviceToHost));
+    auto scan = [&](const DevBuf<uint32_t>& d) -> int {
+        if (!d || !d.cap) return 0;
+        h.resize(d.cap);
+        HIP_TRY(c, hipMemcpy(h.data(), d, d.cap * 4, hipMemcpyDeviceToHost));
         for (uint32_t w : h) n += w != 0xffffffffu;
         return 0;
     };
-    if (scan(c->d_spill, c->spill_capacity) || scan(c->b_spill, c->b_spill_capacity)) return SPCBPT_ERR_HIP;
-    for (int k = 0; k < Context::kMaxRender; k++) if (scan(c->d_spill_rs[k], c->spill_rs_capacity[k])) return SPCBPT_ERR_HIP;
+    if (scan(c->lanes[0].spill) || scan(c->lanes[1].spill)) return SPCBPT_ERR_HIP;
+    for (const auto& sp : c->d_spill_rs) if (scan(sp)) return SPCBPT_ERR_HIP;
     *written = n;
     if (entries_per_thread) *entries_per_thread = c->spill_entries_needed();
     return SPCBPT_OK;
@@ -314,14 +313,14 @@ int spcbpt_debug_trace_bench(spcbpt_ctx* c, const float* rays, int n, int mode, 
     };
     if (rc) { cleanup(); return rc; }
     if (mode >= 1 && !c->d_nodes_q) {   // the quad layout of the same nodes, built once
-        e = dev_alloc(&c->d_nodes_q, (size_t)c->n_nodes * 16);
+        e = c->d_nodes_q.reserve((size_t)c->n_nodes * 16);
         if (e == hipSuccess) { launch_repack_nodes_quad(c->d_nodes, c->d_nodes_q, c->n_nodes, c->stream); e = hipGetLastError(); }
     }
     if (e == hipSuccess && mode == 4 && !c->d_nodes_q2) {   // ... and the same with the scale exponents as signed bytes
-        e = dev_alloc(&c->d_nodes_q2, (size_t)c->n_nodes * 16);
+        e = c->d_nodes_q2.reserve((size_t)c->n_nodes * 16);
         if (e == hipSuccess) { launch_repack_nodes_quad2(c->d_nodes_q, c->d_nodes_q2, c->n_nodes, c->stream); e = hipGetLastError(); }
     }
-    const float* nodes_q = mode == 4 ? c->d_nodes_q2 : c->d_nodes_q;
+    const float* nodes_q = mode == 4 ? c->d_nodes_q2.p : c->d_nodes_q.p;
     const int per_cu = trace_bench_blocks_per_cu(mode, any != 0);
     const int rays_per_block = mode == 0 ? 256 : (mode == 4 ? 64 : 64 << (mode - 1));
     const int blocks = std::max(1, std::min(c->num_cus * per_cu, (n + rays_per_block - 1) / rays_per_block));
@@ -381,9 +380,7 @@ int spcbpt_debug_unit(spcbpt_ctx* c, int op, const uint32_t* in, int in_words, u
     if (e == hipSuccess && d_aux) e = hipMemcpy(d_aux, aux, (size_t)aux_floats * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         KParams kp = c->kp;
-        const int es = c->eset;   // the tables of the last sampler build
-        kp.lvc = c->set_lvc[es]; kp.lvc_sorted = c->set_lvc_sorted[es]; kp.subspace = c->set_subspace[es]; kp.cmfs = c->set_cmfs[es]; kp.guide = c->set_guide[es];
-        kp.jump = reinterpret_cast<const int32_t*>(c->set_vals2[es]); kp.sampler_counts = c->set_counts[es];
+        c->sampler_tables(kp, c->eset);   // the tables of the last sampler build
         kp.counters = nullptr;
         if (op == SPCBPT_UNIT_EYE_STEP) {
             rc = c->ensure_spill(((size_t)n + 255) / 256 * 256);

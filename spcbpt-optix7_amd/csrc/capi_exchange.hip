@@ -9,9 +9,9 @@ extern "C" {
 int spcbpt_lvc_export(spcbpt_ctx* c, void** dv, void** dc, int* cap) {
     CTX_CHECK(c);
     if (!dv || !dc || !cap) return SPCBPT_ERR_INVALID_ARG;
-    if (!c->d_lvc) { c->error = "no LVC allocated"; return SPCBPT_ERR_STATE; }
-    const int b = c->build_set();   // the oldest light pass without a sampler: the shard that is exchanged next
-    *dv = c->set_lvc[b]; *dc = c->set_counts[b]; *cap = (int)c->lvc_capacity;
+    if (!c->sets[c->lset].lvc) { c->error = "no LVC allocated"; return SPCBPT_ERR_STATE; }
+    const CacheSet& S = c->sets[c->build_set()];   // the oldest light pass without a sampler: the shard that is exchanged next
+    *dv = S.lvc; *dc = S.counts; *cap = (int)c->lvc_capacity;
     return SPCBPT_OK;
 }
 
@@ -25,12 +25,13 @@ int spcbpt_lvc_import(spcbpt_ctx* c, const void* verts, int count, int is_device
     int rc = c->ensure_lvc_capacity((size_t)std::max(count, 1));
     if (rc) return rc;
     const int b = c->build_set();
-    if (c->light_lane_of_set[b] != 0) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_light[b], 0));   // the pass that filled this set ran on the second lane
-    if ((const void*)c->set_lvc[b] != verts)
-        HIP_TRY(c, hipMemcpyAsync(c->set_lvc[b], verts, (size_t)count * sizeof(LightVertex), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    CacheSet& S = c->sets[b];
+    if (S.light_lane != 0) HIP_TRY(c, hipStreamWaitEvent(c->stream, S.light.ev, 0));   // the pass that filled this set ran on the second lane
+    if ((const void*)S.lvc.p != verts)
+        HIP_TRY(c, hipMemcpyAsync(S.lvc, verts, (size_t)count * sizeof(LightVertex), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     int* h = c->h_import_counts + 2 * b;   // pinned: the upload may run after this call returns
     h[0] = count; h[1] = 0;
-    HIP_TRY(c, hipMemcpyAsync(c->set_counts[b], h, 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(S.counts, h, 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
     // Host memory: wait for the light stream, the caller may reuse `verts` at once.  Device memory: no wait at all -- the copy
     // is ordered on the light stream; the caller keeps `verts` untouched until a light pass launched AFTER this call has been
     // waited for with spcbpt_sync_light (dist.py alternates two staging buffers, which covers a light pass running one frame
@@ -42,16 +43,8 @@ int spcbpt_lvc_import(spcbpt_ctx* c, const void* verts, int count, int is_device
         HIP_TRY(c, hipEventRecord(ev, c->stream));
         c->import_gen++;
     }
-    HIP_TRY(c, hipEventRecord(c->ev_set_stream[b], c->stream));
-    c->ev_set_touched[b] = true;
-    c->set_count_host[b] = count;
-    c->set_bound[b] = -1;
-    c->light_counts_valid[b] = false;
-    c->light_lane_of_set[b] = 0;   // from here on the set's contents are ordered on `stream`
-    for (auto it = c->built_sets.begin(); it != c->built_sets.end();) it = (*it == b) ? c->built_sets.erase(it) : it + 1;   // a sampler built from the old contents is gone
-    if (b == c->lset) c->lvc_count = count;
-    if (c->keys_set == b) c->keys_ready = false;
-    c->have_sampler = false;
+    HIP_TRY(c, S.on_stream.record(c->stream));
+    c->contents_imported(b, count, -1);
     return SPCBPT_OK;
 }
 

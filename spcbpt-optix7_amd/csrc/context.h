@@ -6,6 +6,7 @@
 #include <deque>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -19,6 +20,100 @@ struct TimedSpan {
     std::string name;
     hipEvent_t a, b;
     hipStream_t s;
+};
+
+template <class T>
+static hipError_t dev_alloc(T** p, size_t n) {
+    *p = nullptr;
+    if (n == 0) n = 1;
+    return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T));
+}
+template <class T>
+static void dev_free(T*& p) {
+    if (p) (void)hipFree((void*)p);
+    p = nullptr;
+}
+
+// A grow-only device buffer that frees itself.  reserve() reallocates (contents lost) only when asked for more elements than it
+// holds; like dev_alloc it never allocates nothing (0 elements -> 1).  The hipFree inside waits for the device by itself; a site
+// that wants that wait spelled out calls sync_all() first.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n) {
+        if (n == 0) n = 1;
+        if (n <= cap) return hipSuccess;
+        release();
+        const hipError_t e = dev_alloc(&p, n);
+        if (e == hipSuccess) cap = n;
+        return e;   // (dev_alloc leaves p null when it fails)
+    }
+    void release() { dev_free(p); cap = 0; }
+    void adopt(T* q, size_t n) { release(); p = q; cap = n; }   // takes over an allocation of n elements made with dev_alloc
+    operator T*() const { return p; }
+};
+
+// An event and whether it has been recorded: waiting for one that never was is a no-op.
+struct Event {
+    hipEvent_t ev = nullptr;
+    bool set = false;
+    hipError_t record(hipStream_t s) {
+        const hipError_t e = hipEventRecord(ev, s);
+        if (e == hipSuccess) set = true;
+        return e;
+    }
+    hipError_t wait_on(hipStream_t s) const { return set ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+};
+
+// One buffer set of the light-vertex cache: the compact cache of one light pass (or import) and the sampler tables built from it.
+// What the eye pass reads exists once per frame in flight: Context::sets is a ring of n_sets of these.
+struct CacheSet {
+    DevBuf<LightVertex> lvc;
+    DevBuf<LightVertex> lvc_sorted;   // the set's cache in its sampler's order (written by the sampler build, read by the eye megakernel)
+    DevBuf<uint32_t> jump;
+    DevBuf<float> cmfs;
+    DevBuf<uint32_t> guide;           // the set's second-stage guide table (layout.h KParams::guide)
+    DevBuf<DSubspace> subspace;
+    int* counts = nullptr;            // [0] vertex_count, [1] path_count: a pointer into Context::d_set_counts_all
+    Event light;                      // light pass + compaction of the set done (recorded on the stream of the pass's lane)
+    Event sampler, render;
+    // the event that marks the end of the last eye kernel that read the set: its own, or -- after a batched eye launch -- the ONE event
+    // recorded for the whole batch (that of the batch's last set).  32 event records between a batch's eye kernel and its film merge
+    // were 0.16 ms of idle GPU per launch (kernel trace of a long run).  Waiting on an event that has meanwhile been recorded again
+    // waits for a LATER eye kernel -- more than needed, never a cycle: everything that kernel depends on was queued before it.
+    int render_event_of = 0;
+    Event on_stream;                  // last work queued on `stream` that reads or writes the set (sampler build, import copy):
+                                      // a light pass on the second lane waits for it before it rewrites the set
+    // Sharded job without host round trips (spcbpt_lvc_export_on / spcbpt_lvc_import_gathered, libspcbpt_mgpu): the all-gathered
+    // shards are compacted on the exchange stream with the totals left on the DEVICE; the sampler build then runs over a host-known
+    // upper bound (`bound`, pad keys sort behind the real items) instead of reading the count back.
+    int bound = -1;                   // >= 0: the set's vertex count lives on the device only, this is its upper bound
+    Event exch;                       // gathered compaction of the set done (recorded on the caller's exchange stream)
+    int count_host = -1;              // vertex count of the set when the host knows it (after an import), else -1
+    bool light_counts_valid = false;  // h_light_counts of the set describe its current contents
+    int light_lane = 0;               // which lane's stream last wrote the set (its `light` event orders it)
+};
+
+// Second light lane.  On one in-order stream light pass, compaction, import copy and sampler build of consecutive frames
+// form a chain of ~1.3 ms per frame -- more than a rank's share of the eye pass costs when the frame is sharded eight ways.
+// With light passes running ahead, every other pass (kernel + compaction) therefore goes to a second stream with its own
+// scratch, counts, key and temp buffers; imports and sampler builds stay on `stream` and wait for the pass's event.
+// Lane 0 is Context::stream; its keys / vals / weights / temp are also the sampler build's, its spill area ensure_spill(., false)'s.
+// Lane 1 is created on first use (ensure_lane_b): highest priority, non-blocking.
+struct LightLane {
+    hipStream_t stream = nullptr;
+    DevBuf<LightVertex> scratch;               // core_count * core_padding
+    DevBuf<int> core_counts, core_offsets;     // core_count + 1
+    DevBuf<uint32_t> keys, vals;               // what the lane's compaction leaves (lane 0: valid for `keys_set` if keys_ready)
+    DevBuf<float> weights;
+    DevBuf<unsigned char> temp;
+    DevBuf<uint32_t> spill;
+    uint32_t* work_counter = nullptr;          // the lane's core queue: its word of d_work_counter
 };
 
 struct Context {
@@ -40,18 +135,9 @@ struct Context {
     int n_render = 2, n_sets = 6;   // n_sets = n_render + 4: one set per eye kernel in flight + the light passes ahead of them
     hipStream_t rstreams[kMaxRender] = {};
     int rk = 0, last_merge_k = -1;
-    float* d_result[kMaxRender] = {};
-    hipEvent_t ev_merge[kMaxRender] = {};
-    bool ev_merge_set[kMaxRender] = {};
-    hipEvent_t ev_sampler[kMaxSets] = {}, ev_render[kMaxSets] = {};
-    bool ev_sampler_set[kMaxSets] = {}, ev_render_set[kMaxSets] = {};
-    // the event that marks the end of the last eye kernel that read the set: its own, or -- after a batched eye launch -- the ONE event
-    // recorded for the whole batch (that of the batch's last set).  32 event records between a batch's eye kernel and its film merge
-    // were 0.16 ms of idle GPU per launch (kernel trace of a long run).  Waiting on an event that has meanwhile been recorded again
-    // waits for a LATER eye kernel -- more than needed, never a cycle: everything that kernel depends on was queued before it.
-    int render_event_of[kMaxSets] = {};
-    hipEvent_t ev_set_stream[kMaxSets] = {};   // last work queued on `stream` that reads or writes the set (sampler build, import copy):
-    bool ev_set_touched[kMaxSets] = {};        // a light pass on the second lane waits for it before it rewrites the set
+    DevBuf<float> d_result[kMaxRender];
+    Event ev_merge[kMaxRender];
+    CacheSet sets[kMaxSets];
     int lset = 0, eset = 0;  // buffer set of the latest light pass, and of the sampler eye launches use
     // Light passes whose sampler has not been built yet, oldest first.  The host loop of a single GPU alternates
     // light pass -> sampler build, so the queue holds one set; a sharded job launches the NEXT frame's light pass before it
@@ -59,70 +145,60 @@ struct Context {
     // exchange makes the host wait for it), so export / import / build_sampler always address the OLDEST pending set.
     std::deque<int> pending;
     bool light_ahead = false;                // spcbpt_set_light_ahead: keep older unbuilt passes queued (default: only the latest)
-    hipEvent_t ev_light[kMaxSets] = {};      // light pass + compaction of the set done (recorded on `stream`)
-    int set_count_host[kMaxSets];            // vertex count of the set when the host knows it (after an import), else -1
-    bool light_counts_valid[kMaxSets] = {};  // h_light_counts of the set describe its current contents
-    int keys_set = -1;                       // the set whose compaction left d_keys / d_vals / d_weights (valid if keys_ready)
-    // Sharded job without host round trips (spcbpt_lvc_export_on / spcbpt_lvc_import_gathered, libspcbpt_mgpu): the all-gathered
-    // shards are compacted on the exchange stream with the totals left on the DEVICE; the sampler build then runs over a host-known
-    // upper bound (`set_bound`, pad keys sort behind the real items) instead of reading the count back.
-    int set_bound[kMaxSets];                 // >= 0: the set's vertex count lives on the device only, this is its upper bound
-    hipEvent_t ev_exch[kMaxSets] = {};       // gathered compaction of the set done (recorded on the caller's exchange stream)
-    bool ev_exch_set[kMaxSets] = {};
+    int keys_set = -1;                       // the set whose compaction left lanes[0].keys / vals / weights (valid if keys_ready)
     int export_on(hipStream_t xs, void** dv, void** dc, int* cap);
     int import_gathered(const void* shards, const int* counts_all, int world, int shard_cap, hipStream_t xs, int nf);
     int export_batch_on(hipStream_t xs, int nf, void* send, int* send_counts, int shard_cap);   // one exchange per light batch
+    int wait_for_contents(hipStream_t xs, int s);
     hipEvent_t ev_import[2] = {};            // device-to-device import copies done (alternating: the caller alternates two staging buffers)
     long long import_gen = 0;
     int* h_import_counts = nullptr;          // pinned [kMaxSets][2]: source of the counts upload of an import (no host wait)
-    int* h_light_counts = nullptr;           // pinned [kMaxSets][2]: (vertex_count, path_count) of a light pass, written on `stream`
-                                             // before ev_light -- the host reads them after waiting for that event only
+    int* h_light_counts = nullptr;           // pinned [kMaxSets][2]: (vertex_count, path_count) of a light pass, written on the lane's
+                                             // stream before the set's `light` event -- the host reads them after waiting for that event only
     int build_set() const { return pending.empty() ? lset : pending.front(); }
-    // Second light lane.  On one in-order stream light pass, compaction, import copy and sampler build of consecutive frames
-    // form a chain of ~1.3 ms per frame -- more than a rank's share of the eye pass costs when the frame is sharded eight ways.
-    // With light passes running ahead, every other pass (kernel + compaction) therefore goes to a second stream with its own
-    // scratch, counts, key and temp buffers; imports and sampler builds stay on `stream` and wait for the pass's event.
-    hipStream_t lstream_b = nullptr;
+    // The transitions of a buffer set, each written once (ctx_light.hip):
+    int begin_rewrite(hipStream_t ls, int s, int& waited_for);   // `ls` waits for the set's readers before a light pass rewrites it
+    void set_rewritten(int s);                                   // its sampler is gone, lane 0's keys no longer describe it
+    int pass_traced(hipStream_t ls, int s, int lane);            // a light pass has been queued into it: unbuilt, at the back of `pending`
+    int sampler_built(int s);                                    // its tables have been queued on `stream`: the set eye launches read
+    void contents_imported(int s, int count_host, int bound);    // an import replaced its contents (ordered on `stream` / by `exch`)
+    template <class P>
+    void sampler_tables(P& d, int s) const {                     // the sampler-table pointers of a KParams / FrameDesc
+        const CacheSet& S = sets[s];
+        d.lvc = S.lvc; d.lvc_sorted = S.lvc_sorted; d.subspace = S.subspace; d.cmfs = S.cmfs; d.guide = S.guide; d.sampler_counts = S.counts;
+        if constexpr (std::is_same<P, KParams>::value) d.jump = reinterpret_cast<const int32_t*>(S.jump.p);
+    }
+    LightLane lanes[2];
     int light_toggle = 0;
-    int light_lane_of_set[kMaxSets] = {};    // which lane's stream last wrote the set (its ev_light orders it)
-    LightVertex* b_scratch = nullptr; size_t b_scratch_capacity = 0;
-    int *b_core_counts = nullptr, *b_core_offsets = nullptr; size_t b_counts_capacity = 0;
-    uint32_t *b_keys = nullptr, *b_vals = nullptr; float* b_weights = nullptr; size_t b_keys_capacity = 0;
-    unsigned char* b_temp = nullptr; size_t b_temp_capacity = 0;
-    uint32_t* b_spill = nullptr; size_t b_spill_capacity = 0;
-    int ensure_lane_b();
+    int ensure_lane_b();   // lane 1 exists and matches the light-pass geometry and the set capacity
+    // the light-pass fields of kp (geometry, frame, scratch, counts, counters) and the spill area of the grid that will run it:
+    // n_frames == 0: one pass (or the probe), a thread per core; n_frames > 0: a batched pass of light_trace_blocks(kp, grid_cap) blocks
+    int light_pass_params(uint32_t frame, int n_frames, LightVertex* scratch, int* core_counts, bool count_events, DevBuf<uint32_t>& spill, int grid_cap);
     // Batched light pass (spcbpt_launch_light_batch): the passes of n consecutive launch frames as ONE persistent launch on the
     // second lane, each into its own set.  A rank of an 8-GPU job traces 1/8 of the cores per frame; its pass is then a ~1.2 ms
     // chain of 50 dependent bounces that the few block slots beside the eye grid run one after the other -- eight of them per eye
     // batch cost more than the eye batch itself.  In one queue they regenerate like one pass of eight times the cores.
-    LightVertex* lb_scratch = nullptr; size_t lb_scratch_capacity = 0;     // n * core_count * core_padding
-    int *lb_core_counts = nullptr, *lb_core_offsets = nullptr, *lb_path_counts = nullptr; size_t lb_counts_capacity = 0;   // n * (core_count + 1)
-    uint32_t* lb_spill = nullptr; size_t lb_spill_capacity = 0;
+    // It has scratch, counts and spill of its own and uses lane 1's stream, temp and queue word.
+    DevBuf<LightVertex> lb_scratch;                                   // n * core_count * core_padding
+    DevBuf<int> lb_core_counts, lb_core_offsets, lb_path_counts;      // n * (core_count + 1); kMaxBatchFrames
+    DevBuf<uint32_t> lb_spill;
     int launch_light_batch(uint32_t first_frame, int n);
-    int* d_set_counts_all = nullptr;         // one allocation behind set_counts[]: set s at + 2 s (a batch copies its sets' counts to the host as ranges)
-    LightVertex* set_lvc[kMaxSets] = {};
-    LightVertex* set_lvc_sorted[kMaxSets] = {};   // the set's cache in its sampler's order (written by the sampler build, read by the eye megakernel)
-    uint32_t* set_vals2[kMaxSets] = {};
-    float* set_cmfs[kMaxSets] = {};
-    uint32_t* set_guide[kMaxSets] = {};   // the set's second-stage guide table (layout.h KParams::guide)
-    DSubspace* set_subspace[kMaxSets] = {};
-    int* set_counts[kMaxSets] = {};
-    uint32_t* d_spill_rs[kMaxRender] = {};   // traversal-stack spill areas of the render streams (d_spill serves `stream`)
-    size_t spill_rs_capacity[kMaxRender] = {};
+    DevBuf<int> d_set_counts_all;            // one allocation behind the sets' `counts`: set s at + 2 s (a batch copies its sets' counts to the
+                                             // host as ranges), and a spare pair behind them (probe_lvc_capacity)
+    DevBuf<uint32_t> d_spill_rs[kMaxRender];   // traversal-stack spill areas of the render streams (lanes[0].spill serves `stream`)
     int sync_all();
-    void select_set(int s);
     std::string error;
     KParams kp;
     // scene
-    float* d_nodes = nullptr;
-    float* d_nodes_q = nullptr;            // the same nodes in the quad-lane layout (quad_trace.hip), built on first use
-    float* d_nodes_q2 = nullptr;           // ... with the scale exponents as signed bytes (the lean quad kernel)
-    float* d_tris = nullptr;
+    DevBuf<float> d_nodes;
+    DevBuf<float> d_nodes_q;               // the same nodes in the quad-lane layout (quad_trace.hip), built on first use
+    DevBuf<float> d_nodes_q2;              // ... with the scale exponents as signed bytes (the lean quad kernel)
+    DevBuf<float> d_tris;
     int n_paired = 0;                      // triangles that are half of a fan pair (lbvh.h): what the pooled pass tests two at a time
-    int32_t* d_tri_orig = nullptr;
-    DMaterial* d_mats = nullptr;
+    DevBuf<int32_t> d_tri_orig;
+    DevBuf<DMaterial> d_mats;
     DLight* d_lights = nullptr;
-    DTexture* d_tex = nullptr;
+    DevBuf<DTexture> d_tex;
     std::vector<uint32_t*> d_tex_data;
     int n_triangles = 0, n_nodes = 0, bvh_depth = 0, n_lights = 0, n_mats = 0;
     // environment map (params.sky; spcbpt_set_environment): device copies of the flipped texture and the sampling CMF
@@ -135,17 +211,17 @@ struct Context {
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};   // of every vertex handed to spcbpt_create (+ the light quads)
     int set_environment(const float* rgba, int w, int h, const float* center, float radius);
     // film
-    float* d_accum = nullptr;
-    uint32_t* d_frame = nullptr;
+    DevBuf<float> d_accum;
+    DevBuf<uint32_t> d_frame;
     bool have_camera = false;
     // subspace tuple
     float* d_eye_tree = nullptr;
     float* d_light_tree = nullptr;
-    float* d_Q = nullptr;
-    float* d_gamma = nullptr;
-    float* d_gamma2 = nullptr;   // three-level copy of d_gamma (layout.h: CMF2_ROW)
-    float* d_gamma_q = nullptr;     // Gamma / Q table (layout.h: KParams::gamma_q)
-    uint16_t* d_guide1 = nullptr;   // first-stage guide table (layout.h: KParams::cmf_guide1)
+    DevBuf<float> d_Q;
+    DevBuf<float> d_gamma;
+    DevBuf<float> d_gamma2;      // three-level copy of d_gamma (layout.h: CMF2_ROW)
+    DevBuf<float> d_gamma_q;     // Gamma / Q table (layout.h: KParams::gamma_q)
+    DevBuf<uint16_t> d_guide1;   // first-stage guide table (layout.h: KParams::cmf_guide1)
     bool gamma_monotone = false; // every row of the installed matrix is a proper CMF: first-stage sampling may count instead of bisect
     std::vector<spcbpt_tree_node> h_eye_tree, h_light_tree;
     std::vector<float> h_Q, h_gamma;
@@ -155,12 +231,6 @@ struct Context {
                                        // (counting) instantiations run instead
     // light pass + LVC + sampler
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 100000, 1};
-    LightVertex* d_scratch = nullptr;
-    size_t scratch_capacity = 0;
-    int* d_core_counts = nullptr;
-    int* d_core_offsets = nullptr;
-    size_t counts_capacity = 0;
-    LightVertex* d_lvc = nullptr;
     // Vertices every buffer set (compact LVC, jump buffer, CMFs) holds.  NOT the padded worst case num_core x core_padding (5.2 M
     // vertices = 541 MB per set at the bench geometry, 53 GB for the 99 sets of a 32-frame pipeline): a light pass fills ~5 % of
     // its padded slots, so the sets are sized from a PROBE pass -- the first light pass after spcbpt_set_light_trace is traced
@@ -172,27 +242,18 @@ struct Context {
     size_t lvc_fixed = 0;            // spcbpt_lvc_set_capacity / SPCBPT_LVC_CAPACITY: explicit capacity (0 = from the probe pass)
     bool lvc_probe_needed = false;   // set by set_light_trace, consumed by the next light pass
     int probe_lvc_capacity();
-    uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_vals = nullptr, *d_vals2 = nullptr;
-    float* d_weights = nullptr;
-    double *d_wsorted = nullptr, *d_prefix = nullptr;
-    float* d_cmfs = nullptr;
-    DSubspace* d_subspace = nullptr;
-    int* d_sampler_counts = nullptr;  // [0] vertex_count, [1] path_count
-    int* d_hist = nullptr;            // per-block histograms / offsets of the four-launch sampler build (kernels.hip)
+    DevBuf<uint32_t> d_keys2;        // the sampler build's own scratch (besides lanes[0].keys / vals / weights / temp), per vertex of a set
+    DevBuf<double> d_wsorted, d_prefix;
+    DevBuf<int> d_hist;               // per-block histograms / offsets of the four-launch sampler build (kernels.hip)
     bool counting_build = true;       // SPCBPT_SAMPLER_BUILD=hipcub selects the radix-sort form (same tables)
     int lvc_count = 0, path_count = 0;
     bool keys_ready = false, have_sampler = false;
-    // scratch
-    unsigned char* d_temp = nullptr;
-    size_t temp_capacity = 0;
-    uint32_t* d_spill = nullptr;
-    size_t spill_capacity = 0;
-    uint32_t* d_diag = nullptr;        // KParams::diag: [0] dropped traversal-stack entries, [1] shard / gathered-cache overflow of exchange 1, [2] a light pass outgrew the set capacity
+    DevBuf<uint32_t> d_diag;           // KParams::diag: [0] dropped traversal-stack entries, [1] shard / gathered-cache overflow of exchange 1, [2] a light pass outgrew the set capacity
     int spill_entries_debug = -1;      // SPCBPT_DEBUG_SPILL_ENTRIES: caps the spill entries per thread (tests of the overflow report)
     int spill_entries_needed() const;  // 3 * bvh_depth - kStackLds (a 4-wide node pushes up to 3 children per level)
     int check_diag();                  // after a sync: SPCBPT_ERR_STATE if a kernel dropped stack entries since the last check
     // instrumentation
-    uint32_t* d_work_counter = nullptr;
+    DevBuf<uint32_t> d_work_counter;   // tile queues of the render streams, then the core queues of the two light lanes
     int num_cus = 0, blocks_per_cu[3] = {0, 0, 0};   // per kernel variant (single-frame launches), of the instantiation launched
     int blocks_per_cu_batch = 0;                       // the batched timed kernel's
     int grid_percent = 0;              // persistent grid as a share of the resident block slots; 0 = 94 with several render streams, else 100 (launch_render)
@@ -200,7 +261,7 @@ struct Context {
     int light_blocks = -1;             // persistent grid of the light pass (SPCBPT_LIGHT_BLOCKS; default: one block per CU)
     int light_batch_blocks = -1;       // ... of a batched light pass (SPCBPT_LIGHT_BATCH_BLOCKS; 0 = in proportion to the light paths per pixel, >= 16: launch_light_batch)
     int tiles_per_wave = 1;            // lower bound of 8x8 tiles per persistent wave (SPCBPT_TILES_PER_WAVE)
-    unsigned long long* d_counters = nullptr;
+    DevBuf<unsigned long long> d_counters;
     bool counting = false, timing = false;
     bool count_executed = false;       // spcbpt_enable_counters(ctx, 2): count with the TIMED kernels' instantiations (label caching) instead of the reference's order
     int kernel_variant() const { return tree_has_direction ? 1 : (counting ? (count_executed ? 2 : 1) : 0); }   // kernels.h: launch_spcbpt
@@ -223,14 +284,14 @@ struct Context {
     int fetch_counts_of(int set);
     int build_sampler();
     int build_sampler_batch(int n);   // the n oldest pending passes in one set of four launches (capi.hip)
-    uint32_t* sbb_keys = nullptr; float* sbb_weights = nullptr; double* sbb_wsorted = nullptr; int* sbb_hist = nullptr;   // its scratch: per frame what d_keys .. d_hist are
+    DevBuf<uint32_t> sbb_keys; DevBuf<float> sbb_weights; DevBuf<double> sbb_wsorted; DevBuf<int> sbb_hist;   // its scratch: per frame what lanes[0].keys .. d_hist are
     int sbb_frames = 0; size_t sbb_capacity = 0;   // frames x items per frame it holds
     int sbb_fallbacks = 0;                          // batches built one by one because the scratch could not be allocated
     size_t sbb_refused_bytes = 0;                   // the smallest scratch size the device has refused (0: none): not asked for again until the capacity or the mode changes
     void free_batch_build_scratch();
     size_t sbb_debug_limit() const;
     // the tables of the last sampler build are still what that build left (no later pass, import or re-allocation took the set)
-    bool sampler_intact() const { return !built_sets.empty() && built_sets.back() == eset && ev_sampler_set[eset]; }
+    bool sampler_intact() const { return !built_sets.empty() && built_sets.back() == eset && sets[eset].sampler.set; }
     int launch_render(const char* name, bool spcbpt_alg, uint32_t frame, int r0, int r1, int rs, bool full_mis = false, bool defer_merge = false);
     // spcbpt_launch_deferred: a render launch whose film merge (running mean + tone map from its `result` buffer) has not been queued:
     // the frame is either merged later (merge_deferred(true)) or never (false) -- the interactive loop's speculative next frame
@@ -242,8 +303,8 @@ struct Context {
     // about one per resident wave, i.e. all drain phase; four frames in one queue regenerate like one frame four times the size.
     std::deque<int> built_sets;                                  // sets of the most recent sampler builds, oldest first
     int eye_batch = 1;                                           // frames per batched launch the context is sized for (SPCBPT_EYE_BATCH)
-    float* d_result_b[kMaxRender][kMaxBatchFrames] = {};         // per render stream and frame slot: radiance of that frame
-    FrameDesc* d_frames[kMaxRender] = {};                        // device copies of the batch descriptors
+    DevBuf<float> d_result_b[kMaxRender][kMaxBatchFrames];       // per render stream and frame slot: radiance of that frame
+    DevBuf<FrameDesc> d_frames[kMaxRender];                      // device copies of the batch descriptors
     static const int kDescRing = 4;
     FrameDesc* h_frames = nullptr;                               // pinned [kMaxRender][kDescRing][kMaxBatchFrames]: descriptor uploads in flight
     hipEvent_t ev_desc[kMaxRender][kDescRing] = {};              // upload out of that pinned slot done
@@ -251,18 +312,22 @@ struct Context {
     int launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs);
     // "lt" (ctx_splat.hip): the cache of set `eset` splatted onto the film.  One splat buffer (float4 per pixel, summed with float
     // atomics) per render stream, allocated at the first "lt" launch of that stream after a resize.
-    float* d_splat[kMaxRender] = {};
-    size_t splat_px[kMaxRender] = {};   // pixels d_splat[k] holds
+    DevBuf<float> d_splat[kMaxRender];
     int launch_splat(uint32_t frame, int r0, int r1, int rs);
+    // Prologue and epilogue of the launches that end in a film merge (ctx_render.hip)
+    int film_ready();                          // no deferred frame outstanding, a film, a camera
+    int begin_render(int r0, int r1, int rs);  // the band of rows into kp, then the next render stream
+    void next_render_stream();                 // consecutive render launches rotate through the render streams
+    int chain_wait();    // `rstream` behind the last link of the film-merge chain
+    int chain_end();     // ... and this launch as the chain's last link
+    int render_done(int s);   // the eye kernel just queued on `rstream` is the last reader of set s
     int finish_frame();
     // First-hit feature buffers and the denoiser's planes (ctx_features.hip): float4 per pixel each, allocated at the first feature
     // launch / the first denoise after a resize (spcbpt_resize frees them), so a context that asks for neither keeps its footprint.
-    float *d_feat_albedo = nullptr, *d_feat_normal_depth = nullptr;   // running means of (base colour, coverage) / (normal, depth)
-    float *d_dn_position = nullptr, *d_dn_ping = nullptr, *d_dn_pong = nullptr, *d_denoised = nullptr;
-    uint32_t* d_denoised_frame = nullptr;                             // RGBA8: the film's tone map of d_denoised
+    DevBuf<float> d_feat_albedo, d_feat_normal_depth;                 // running means of (base colour, coverage) / (normal, depth)
+    DevBuf<float> d_dn_position, d_dn_ping, d_dn_pong, d_denoised;
+    DevBuf<uint32_t> d_denoised_frame;                                // RGBA8: the film's tone map of d_denoised
     bool have_features = false, have_denoised = false;                // ... since the last resize
-    int chain_begin();   // the next render stream, behind the last link of the film-merge chain
-    int chain_end();     // ... and this launch as the chain's last link
     int launch_features(uint32_t subframe, int r0, int r1, int rs);
     int denoise(const spcbpt_denoise_params& p);
     void free_features();

@@ -9,25 +9,13 @@ using namespace spc;
 
 namespace spc {
 
-// Both passes are links of the film-merge chain (finish_frame): they take the next render stream, wait for the last link queued and
-// leave ev_merge behind for the next one.  So the running means of consecutive feature launches are applied in launch order, a
-// denoise sees every merge queued before it, and no later merge rewrites the film under it -- the order a "pt" launch's merge has.
-int Context::chain_begin() {
-    rk = (rk + 1) % n_render;
-    rstream = rstreams[rk];
-    if (last_merge_k >= 0 && last_merge_k != rk && rstreams[last_merge_k] != rstream) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_merge[last_merge_k], 0));
-    return 0;
-}
-int Context::chain_end() {
-    HIP_TRY(this, hipEventRecord(ev_merge[rk], rstream));
-    ev_merge_set[rk] = true;
-    last_merge_k = rk;
-    return 0;
-}
-
+// Both passes are links of the film-merge chain (ctx_render.hip: chain_wait / chain_end): they take the next render stream, wait for the
+// last link queued and leave ev_merge behind for the next one.  So the running means of consecutive feature launches are applied in
+// launch order, a denoise sees every merge queued before it, and no later merge rewrites the film under it -- the order a "pt"
+// launch's merge has.
 void Context::free_features() {
-    dev_free(d_feat_albedo); dev_free(d_feat_normal_depth);
-    dev_free(d_dn_position); dev_free(d_dn_ping); dev_free(d_dn_pong); dev_free(d_denoised); dev_free(d_denoised_frame);
+    d_feat_albedo.release(); d_feat_normal_depth.release();
+    d_dn_position.release(); d_dn_ping.release(); d_dn_pong.release(); d_denoised.release(); d_denoised_frame.release();
     have_features = have_denoised = false;
 }
 
@@ -38,13 +26,14 @@ int Context::launch_features(uint32_t subframe, int r0, int r1, int rs) {
     if (!have_camera) { error = "launch_features before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
     if (rs < 1) rs = 1;
     if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
-    if (int rc = chain_begin()) return rc;
+    next_render_stream();
+    if (int rc = chain_wait()) return rc;
     // the buffers: allocated (and zeroed, for the rows a banded launch leaves alone) at the first feature launch after a resize, so
     // that a context that never asks for features keeps its footprint (spcbpt_resize has freed those of the old size)
     const size_t px = (size_t)kp.width * kp.height;
     if (!d_feat_albedo) {
-        HIP_TRY(this, dev_alloc(&d_feat_albedo, px * 4));
-        HIP_TRY(this, dev_alloc(&d_feat_normal_depth, px * 4));
+        HIP_TRY(this, d_feat_albedo.reserve(px * 4));
+        HIP_TRY(this, d_feat_normal_depth.reserve(px * 4));
         HIP_TRY(this, hipMemsetAsync(d_feat_albedo, 0, px * 16, rstream));
         HIP_TRY(this, hipMemsetAsync(d_feat_normal_depth, 0, px * 16, rstream));
     }
@@ -78,14 +67,15 @@ int Context::denoise(const spcbpt_denoise_params& dp) {
     const float sigma_c = dp.sigma_c > 0.0f ? dp.sigma_c : SPCBPT_DENOISE_SIGMA_C;
     const float sigma_n = dp.sigma_n > 0.0f ? dp.sigma_n : SPCBPT_DENOISE_SIGMA_N;
     const float sigma_x = dp.sigma_x > 0.0f ? dp.sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
-    if (int rc = chain_begin()) return rc;
+    next_render_stream();
+    if (int rc = chain_wait()) return rc;
     const size_t px = (size_t)kp.width * kp.height;
     if (!d_denoised) {
-        HIP_TRY(this, dev_alloc(&d_dn_position, px * 4));
-        HIP_TRY(this, dev_alloc(&d_dn_ping, px * 4));
-        HIP_TRY(this, dev_alloc(&d_dn_pong, px * 4));
-        HIP_TRY(this, dev_alloc(&d_denoised_frame, px));
-        HIP_TRY(this, dev_alloc(&d_denoised, px * 4));
+        HIP_TRY(this, d_dn_position.reserve(px * 4));
+        HIP_TRY(this, d_dn_ping.reserve(px * 4));
+        HIP_TRY(this, d_dn_pong.reserve(px * 4));
+        HIP_TRY(this, d_denoised_frame.reserve(px));
+        HIP_TRY(this, d_denoised.reserve(px * 4));
     }
     DenoiseParams q;
     memset(&q, 0, sizeof(q));

@@ -6,11 +6,46 @@ using namespace spc;
 
 namespace spc {
 
-int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, int r0, int r1, int rs, bool full_mis, bool defer_merge) {
+// What every launch that ends in a film merge needs before anything else ...
+int Context::film_ready() {
     if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (defer_merge && (full_mis || counting)) { error = "launch_deferred: plain \"pt\" / \"SPCBPT_eye\" launches only"; return SPCBPT_ERR_INVALID_ARG; }
     if (!d_accum) { error = "render before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!have_camera) { error = "render before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
+    return 0;
+}
+// ... and, once the launch's own checks have passed: the band of rows, and the next render stream (see context.h)
+int Context::begin_render(int r0, int r1, int rs) {
+    if (rs < 1) rs = 1;
+    if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
+    kp.row_begin = r0; kp.row_end = std::min(r1, (int)kp.height); kp.row_step = rs;
+    next_render_stream();
+    return 0;
+}
+void Context::next_render_stream() {
+    rk = (rk + 1) % n_render;
+    rstream = rstreams[rk];
+}
+// Links of the film-merge chain (the only cross-frame ordering): a link waits for the last one queued and leaves ev_merge behind for
+// the next.  Film merges, feature launches and denoise passes are links (ctx_features.hip).
+int Context::chain_wait() {
+    if (last_merge_k >= 0 && last_merge_k != rk && rstreams[last_merge_k] != rstream) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_merge[last_merge_k].ev, 0));
+    return 0;
+}
+int Context::chain_end() {
+    HIP_TRY(this, ev_merge[rk].record(rstream));
+    last_merge_k = rk;
+    return 0;
+}
+int Context::render_done(int s) {
+    sets[s].render_event_of = s;
+    HIP_TRY(this, sets[s].render.record(rstream));
+    return 0;
+}
+
+int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, int r0, int r1, int rs, bool full_mis, bool defer_merge) {
+    // (`!deferred.active`: film_ready's deferred-frame error keeps coming first, as it always has)
+    if (!deferred.active && defer_merge && (full_mis || counting)) { error = "launch_deferred: plain \"pt\" / \"SPCBPT_eye\" launches only"; return SPCBPT_ERR_INVALID_ARG; }
+    if (int rc = film_ready()) return rc;
     if (spcbpt_alg && (!have_sampler || !have_subspace)) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
     // the counting forms of the eye kernel know no sky strategy: a counted frame would render without it
     if (spcbpt_alg && !full_mis && kernel_variant() != 0 && eye_sees_sky(kp)) {
@@ -18,20 +53,17 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
                 "eye-sees-sky strategy: clear SPCBPT_ENV_EYE_SEES_SKY (spcbpt_set_environment_mode) for this launch";
         return SPCBPT_ERR_STATE;
     }
-    if (rs < 1) rs = 1;
-    if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
-    kp.subframe = frame; kp.row_begin = r0; kp.row_end = std::min(r1, (int)kp.height); kp.row_step = rs;
-    kp.counters = counting ? d_counters : nullptr;
-    rk = (rk + 1) % n_render;   // consecutive render launches rotate through the render streams (see context.h)
-    rstream = rstreams[rk];
+    int rc = begin_render(r0, r1, rs);
+    if (rc) return rc;
+    kp.subframe = frame;
+    kp.counters = counting ? d_counters.p : nullptr;
     kp.result = d_result[rk];
     if (spcbpt_alg) {
         // the sampler tables this launch reads (set `eset`) were built on `stream`
-        kp.lvc = set_lvc[eset]; kp.lvc_sorted = set_lvc_sorted[eset]; kp.subspace = set_subspace[eset]; kp.cmfs = set_cmfs[eset]; kp.guide = set_guide[eset];
-        kp.jump = reinterpret_cast<const int32_t*>(set_vals2[eset]); kp.sampler_counts = set_counts[eset];
-        if (rstream != stream && ev_sampler_set[eset]) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_sampler[eset], 0));
+        sampler_tables(kp, eset);
+        if (rstream != stream) HIP_TRY(this, sets[eset].sampler.wait_on(rstream));
     }
-    int rc = ensure_spill((size_t)render_thread_count(kp), true);
+    rc = ensure_spill((size_t)render_thread_count(kp), true);
     if (rc) return rc;
     if (full_mis && kp.scene.env.valid) { error = "SPCBPT_no_rmis: not with an environment map (the full-path weights of cuProg.h:901-1105 know area lights only)"; return SPCBPT_ERR_STATE; }
     if (full_mis) {   // "SPCBPT_no_rmis": a plain one-lane-per-pixel launch over the same sampler tables
@@ -39,10 +71,8 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
         launch_spcbpt_no_rmis(kp, rstream);
         time_end();
         HIP_TRY(this, hipGetLastError());
-        render_event_of[eset] = eset;
-        HIP_TRY(this, hipEventRecord(ev_render[eset], rstream));
-        ev_render_set[eset] = true;
-        return finish_frame();
+        rc = render_done(eset);
+        return rc ? rc : finish_frame();
     }
     if (spcbpt_alg) {
         kp.n_tiles = (uint32_t)render_tile_count(kp);
@@ -78,11 +108,7 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
     else launch_pt(kp, counting, rstream);
     time_end();
     HIP_TRY(this, hipGetLastError());
-    if (spcbpt_alg) {
-        render_event_of[eset] = eset;
-        HIP_TRY(this, hipEventRecord(ev_render[eset], rstream));
-        ev_render_set[eset] = true;
-    }
+    if (spcbpt_alg && (rc = render_done(eset))) return rc;
     if (defer_merge) {
         deferred.active = true; deferred.rk = rk; deferred.subframe = kp.subframe; deferred.result = kp.result;
         deferred.row_begin = kp.row_begin; deferred.row_end = kp.row_end; deferred.row_step = kp.row_step;
@@ -106,14 +132,13 @@ int Context::merge_deferred(bool keep) {
 // Host wait for the last film merge only (the frame to be displayed), not for work queued behind it (the next frame's light
 // pass, sampler build and speculative eye launch).
 int Context::sync_film() {
-    if (last_merge_k >= 0 && ev_merge_set[last_merge_k]) HIP_TRY(this, hipEventSynchronize(ev_merge[last_merge_k]));
+    if (last_merge_k >= 0 && ev_merge[last_merge_k].set) HIP_TRY(this, hipEventSynchronize(ev_merge[last_merge_k].ev));
     return check_diag();
 }
 
 int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs) {
-    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (!d_accum) { error = "render before spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (!have_camera) { error = "render before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
+    int rc = film_ready();
+    if (rc) return rc;
     if (!have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
     if (n < 1 || n > kMaxBatchFrames || !subframes) { error = "launch_eye_batch: 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
     if (n > (int)built_sets.size()) { error = "launch_eye_batch: fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }
@@ -122,30 +147,24 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
     if (counting) { error = "launch_eye_batch: not with event counters enabled (count with spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
     if (tree_has_direction) { error = "launch_eye_batch: the batched kernel caches vertex labels, which needs classifier trees without direction nodes (use spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
     if (kp.width >= 65536u || kp.height >= 65536u) { error = "launch_eye_batch: image too large"; return SPCBPT_ERR_INVALID_ARG; }
-    if (rs < 1) rs = 1;
-    if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
-    kp.row_begin = r0; kp.row_end = std::min(r1, (int)kp.height); kp.row_step = rs;
+    if ((rc = begin_render(r0, r1, rs))) return rc;
     kp.counters = nullptr;
-    rk = (rk + 1) % n_render;
-    rstream = rstreams[rk];
     const size_t px = (size_t)kp.width * kp.height;
     if (!h_frames) HIP_TRY(this, hipHostMalloc(reinterpret_cast<void**>(&h_frames), sizeof(FrameDesc) * kMaxRender * kDescRing * kMaxBatchFrames));
-    if (!d_frames[rk]) HIP_TRY(this, hipMalloc(reinterpret_cast<void**>(&d_frames[rk]), sizeof(FrameDesc) * kMaxBatchFrames));
+    HIP_TRY(this, d_frames[rk].reserve(kMaxBatchFrames));
     // the descriptors travel through a small ring of pinned slots: the host must not wait for the previous batch of this stream
     // (it would stop launching the light passes of the batches after it), only for the upload that used this slot 4 batches ago
     const int gen = desc_gen[rk]++ % kDescRing;
     FrameDesc* hf = h_frames + ((size_t)rk * kDescRing + gen) * kMaxBatchFrames;
     if (ev_desc[rk][gen]) HIP_TRY(this, hipEventSynchronize(ev_desc[rk][gen]));
     else HIP_TRY(this, hipEventCreateWithFlags(&ev_desc[rk][gen], hipEventDisableTiming));
-    int sets[kMaxBatchFrames];
+    int batch[kMaxBatchFrames];
     for (int k = 0; k < n; k++) {
-        const int e = built_sets[built_sets.size() - (size_t)n + (size_t)k];   // oldest of the last n first
-        sets[k] = e;
-        if (!d_result_b[rk][k]) HIP_TRY(this, dev_alloc(&d_result_b[rk][k], px * 4));
-        hf[k].lvc = set_lvc[e]; hf[k].lvc_sorted = set_lvc_sorted[e]; hf[k].subspace = set_subspace[e]; hf[k].cmfs = set_cmfs[e]; hf[k].guide = set_guide[e];
-        hf[k].sampler_counts = set_counts[e];
+        const int e = batch[k] = built_sets[built_sets.size() - (size_t)n + (size_t)k];   // oldest of the last n first
+        HIP_TRY(this, d_result_b[rk][k].reserve(px * 4));
+        sampler_tables(hf[k], e);
         hf[k].result = d_result_b[rk][k]; hf[k].subframe = subframes[k];
-        if (rstream != stream && ev_sampler_set[e]) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_sampler[e], 0));
+        if (rstream != stream) HIP_TRY(this, sets[e].sampler.wait_on(rstream));
     }
     HIP_TRY(this, hipMemcpyAsync(d_frames[rk], hf, sizeof(FrameDesc) * (size_t)n, hipMemcpyHostToDevice, rstream));
     HIP_TRY(this, hipEventRecord(ev_desc[rk][gen], rstream));
@@ -163,17 +182,17 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
     if (percent < 100) max_blocks = std::max(1, max_blocks * percent / 100);
     // the spill area is indexed by the thread of the grid ACTUALLY launched: n frames' tiles, capped by the resident slots
     // (sizing it for one frame's tiles let the blocks beyond one frame's share write past its end whenever that share was below max_blocks)
-    int rc = ensure_spill((size_t)spcbpt_batch_blocks(kp, max_blocks) * (size_t)spcbpt_block_threads(), true);
+    rc = ensure_spill((size_t)spcbpt_batch_blocks(kp, max_blocks) * (size_t)spcbpt_block_threads(), true);
     if (rc) return rc;
     time_begin("spcbpt_render", rstream);
     launch_spcbpt_batch(kp, max_blocks, rstream);
     time_end();
     HIP_TRY(this, hipGetLastError());
-    HIP_TRY(this, hipEventRecord(ev_render[sets[n - 1]], rstream));   // ONE event for the sets of the batch (context.h: render_event_of)
-    for (int k = 0; k < n; k++) { render_event_of[sets[k]] = sets[n - 1]; ev_render_set[sets[k]] = true; }
-    eset = sets[n - 1];
+    eset = batch[n - 1];
+    HIP_TRY(this, sets[eset].render.record(rstream));   // ONE event for the sets of the batch (context.h: CacheSet::render_event_of)
+    for (int k = 0; k < n; k++) { sets[batch[k]].render_event_of = eset; sets[batch[k]].render.set = true; }
     // the frames' merges, in frame order, after the previous launch's merge
-    if (last_merge_k >= 0 && last_merge_k != rk && rstreams[last_merge_k] != rstream) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_merge[last_merge_k], 0));
+    if ((rc = chain_wait())) return rc;
     {   // ... as one pass over the pixels (kernels.hip: k_film_merge_batch -- the operations of n merges, per pixel in frame order)
         MergeBatch mb = {};
         for (int k = 0; k < n; k++) { mb.result[k] = d_result_b[rk][k]; mb.subframe[k] = subframes[k]; }
@@ -183,21 +202,15 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
         HIP_TRY(this, hipGetLastError());
     }
     kp.frames = nullptr; kp.n_frames = 0;
-    HIP_TRY(this, hipEventRecord(ev_merge[rk], rstream));
-    ev_merge_set[rk] = true;
-    last_merge_k = rk;
-    return 0;
+    return chain_end();
 }
 
 // merge this launch's `result` into accum / frame, after the previous launch's merge (the only cross-frame ordering)
 int Context::finish_frame() {
-    if (last_merge_k >= 0 && last_merge_k != rk && rstreams[last_merge_k] != rstream) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_merge[last_merge_k], 0));
+    if (int rc = chain_wait()) return rc;
     launch_film_merge(kp, rstream);
     HIP_TRY(this, hipGetLastError());
-    HIP_TRY(this, hipEventRecord(ev_merge[rk], rstream));
-    ev_merge_set[rk] = true;
-    last_merge_k = rk;
-    return 0;
+    return chain_end();
 }
 
 }  // namespace spc

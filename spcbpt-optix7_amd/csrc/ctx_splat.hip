@@ -10,38 +10,30 @@ namespace spc {
 
 // spcbpt_launch(ctx, "lt", ...): the cache of the sampler set an eye launch would read (`eset`), splatted onto the rows of the band
 // set and merged into the film as this subframe.  Stream and event discipline are launch_render's: the launch takes the next render
-// stream, waits for the set's sampler build, and records ev_render[eset] so that no later light pass rewrites the set under it.
+// stream, waits for the set's sampler build, and records sets[eset].render so that no later light pass rewrites the set under it.
 // Event counters (spcbpt_enable_counters) are left untouched: the splat kernel charges none.
 int Context::launch_splat(uint32_t frame, int r0, int r1, int rs) {
-    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (!d_accum) { error = "render before spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (!have_camera) { error = "render before spcbpt_set_camera"; return SPCBPT_ERR_STATE; }
+    int rc = film_ready();
+    if (rc) return rc;
     if (kp.scene.env.valid) {
         error = "lt: not with an environment map: the directly seen sky is not sampled by this estimator, and the sky vertices of the cache "
                 "(SPCBPT_LV_DIRECTION) have no position to project";
         return SPCBPT_ERR_STATE;
     }
     if (!have_sampler) { error = "lt needs a built sampler (\"light trace\" -> spcbpt_build_sampler)"; return SPCBPT_ERR_STATE; }
-    if (rs < 1) rs = 1;
-    if (r0 < 0 || (r0 % 8) != 0) { error = "row_begin must be a non-negative multiple of 8 (8-row bands)"; return SPCBPT_ERR_INVALID_ARG; }
-    kp.subframe = frame; kp.row_begin = r0; kp.row_end = std::min(r1, (int)kp.height); kp.row_step = rs;
-    rk = (rk + 1) % n_render;
-    rstream = rstreams[rk];
+    if ((rc = begin_render(r0, r1, rs))) return rc;
+    kp.subframe = frame;
     kp.result = d_result[rk];
-    if (rstream != stream && ev_sampler_set[eset]) HIP_TRY(this, hipStreamWaitEvent(rstream, ev_sampler[eset], 0));
+    if (rstream != stream) HIP_TRY(this, sets[eset].sampler.wait_on(rstream));
     // the splat buffer of this render stream: allocated at the first "lt" launch after a resize, so that a context that never
     // launches "lt" keeps its footprint (spcbpt_resize has synchronised every stream before the size changed)
     const size_t px = (size_t)kp.width * kp.height;
-    if (splat_px[rk] != px) {
-        dev_free(d_splat[rk]);
-        splat_px[rk] = 0;
-        HIP_TRY(this, dev_alloc(&d_splat[rk], px * 4));
-        splat_px[rk] = px;
-    }
+    if (d_splat[rk].cap != px * 4) d_splat[rk].release();   // (not grow-only: a smaller film gets a smaller buffer)
+    HIP_TRY(this, d_splat[rk].reserve(px * 4));
     const int capacity = (int)std::min<size_t>(lvc_capacity, 0x7fffffff);
     const int threads = splat_block_threads();
     const int blocks = splat_blocks(std::min(4 * std::max(1, num_cus), (capacity + threads - 1) / threads));
-    int rc = ensure_spill((size_t)blocks * (size_t)threads, true);
+    rc = ensure_spill((size_t)blocks * (size_t)threads, true);
     if (rc) return rc;
     SplatParams sp;
     memset(&sp, 0, sizeof(sp));
@@ -49,7 +41,7 @@ int Context::launch_splat(uint32_t frame, int r0, int r1, int rs) {
     memcpy(sp.eye, kp.eye, 12); memcpy(sp.U, kp.U, 12); memcpy(sp.V, kp.V, 12); memcpy(sp.W, kp.W, 12);
     sp.width = kp.width; sp.height = kp.height; sp.subframe = kp.subframe;
     sp.row_begin = kp.row_begin; sp.row_end = kp.row_end; sp.row_step = kp.row_step;
-    sp.lvc = set_lvc[eset]; sp.sampler_counts = set_counts[eset]; sp.capacity = capacity;
+    sp.lvc = sets[eset].lvc; sp.sampler_counts = sets[eset].counts; sp.capacity = capacity;
     sp.splat = d_splat[rk]; sp.result = kp.result;
     sp.spill = kp.spill; sp.spill_entries = kp.spill_entries; sp.diag = kp.diag;
     HIP_TRY(this, hipMemsetAsync(d_splat[rk], 0, px * 16, rstream));
@@ -58,10 +50,8 @@ int Context::launch_splat(uint32_t frame, int r0, int r1, int rs) {
     launch_lt_resolve(sp, rstream);
     time_end();
     HIP_TRY(this, hipGetLastError());
-    render_event_of[eset] = eset;
-    HIP_TRY(this, hipEventRecord(ev_render[eset], rstream));
-    ev_render_set[eset] = true;
-    return finish_frame();
+    rc = render_done(eset);
+    return rc ? rc : finish_frame();
 }
 
 }  // namespace spc

@@ -22,14 +22,10 @@ void Context::time_end() {
 }
 int Context::sync_all() {
     HIP_TRY(this, hipStreamSynchronize(stream));
-    if (lstream_b) HIP_TRY(this, hipStreamSynchronize(lstream_b));
+    if (lanes[1].stream) HIP_TRY(this, hipStreamSynchronize(lanes[1].stream));
     for (int k = 0; k < n_render; k++)
         if (rstreams[k] && rstreams[k] != stream) HIP_TRY(this, hipStreamSynchronize(rstreams[k]));
     return 0;
-}
-// the members d_lvc / d_vals2 / d_cmfs / d_subspace / d_sampler_counts always name the set of the light pass in progress
-void Context::select_set(int s) {
-    d_lvc = set_lvc[s]; d_vals2 = set_vals2[s]; d_cmfs = set_cmfs[s]; d_subspace = set_subspace[s]; d_sampler_counts = set_counts[s];
 }
 void Context::resolve_spans() {
     for (auto& sp : spans) {
@@ -77,14 +73,8 @@ int Context::ensure_spill(size_t threads, bool render) {
     const int entries = spill_entries_needed();
     kp.spill_entries = entries;
     if (entries == 0) { kp.spill = nullptr; return 0; }
-    const size_t need = threads * (size_t)entries;
-    uint32_t*& buf = render ? d_spill_rs[rk] : d_spill;   // one area per stream: kernels of all three may be in flight together
-    size_t& cap = render ? spill_rs_capacity[rk] : spill_capacity;
-    if (need > cap) {
-        dev_free(buf);   // hipFree waits for the device
-        HIP_TRY(this, dev_alloc(&buf, need));
-        cap = need;
-    }
+    DevBuf<uint32_t>& buf = render ? d_spill_rs[rk] : lanes[0].spill;   // one area per stream: kernels of all three may be in flight together
+    HIP_TRY(this, buf.reserve(threads * (size_t)entries));               // (growing frees the old area: hipFree waits for the device)
     kp.spill = buf;
     return 0;
 }
@@ -141,8 +131,8 @@ int Context::install_subspace(const spcbpt_tree_node* et, int ne, const spcbpt_t
     for (int i = 0; i < nl; i++) if (!lt[i].leaf && lt[i].type == 2) tree_has_direction = true;
     h_Q.assign(q, q + SPCBPT_NUM_SUBSPACE);
     h_gamma.assign(g, g + (size_t)SPCBPT_NUM_SUBSPACE * SPCBPT_NUM_SUBSPACE);
-    if (!d_Q) HIP_TRY(this, dev_alloc(&d_Q, SPCBPT_NUM_SUBSPACE));
-    if (!d_gamma) HIP_TRY(this, dev_alloc(&d_gamma, (size_t)SPCBPT_NUM_SUBSPACE * SPCBPT_NUM_SUBSPACE));
+    HIP_TRY(this, d_Q.reserve(SPCBPT_NUM_SUBSPACE));
+    HIP_TRY(this, d_gamma.reserve((size_t)SPCBPT_NUM_SUBSPACE * SPCBPT_NUM_SUBSPACE));
     HIP_TRY(this, hipMemcpyAsync(d_Q, h_Q.data(), h_Q.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(this, hipMemcpyAsync(d_gamma, h_gamma.data(), h_gamma.size() * 4, hipMemcpyHostToDevice, stream));
     {   // three-level copy for first-stage sampling (device_lib.h: sample_first_stage3; layout.h: CMF2_*)
@@ -154,7 +144,7 @@ int Context::install_subspace(const spcbpt_tree_node* et, int ne, const spcbpt_t
             for (int m = 0; m < CMF2_MID; m++) row[CMF2_COARSE + m] = fine[8 * m + 7];
             for (int k = 0; k < CMF2_COARSE; k++) row[k] = fine[64 * k + 63];
         }
-        if (!d_gamma2) HIP_TRY(this, dev_alloc(&d_gamma2, two.size()));
+        HIP_TRY(this, d_gamma2.reserve(two.size()));
         HIP_TRY(this, hipMemcpy(d_gamma2, two.data(), two.size() * sizeof(float), hipMemcpyHostToDevice));
         {   // gamma_ss as a table (layout.h: KParams::gamma_q): the device's own FP32 subtraction and division, done once here
             std::vector<float> gq((size_t)SPCBPT_NUM_SUBSPACE * SPCBPT_NUM_SUBSPACE);
@@ -165,7 +155,7 @@ int Context::install_subspace(const spcbpt_tree_node* et, int ne, const spcbpt_t
                     gq[(size_t)e * SPCBPT_NUM_SUBSPACE + l] = g / h_Q[l];
                 }
             }
-            if (!d_gamma_q) HIP_TRY(this, dev_alloc(&d_gamma_q, gq.size()));
+            HIP_TRY(this, d_gamma_q.reserve(gq.size()));
             HIP_TRY(this, hipMemcpy(d_gamma_q, gq.data(), gq.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         {   // first-stage guide table (layout.h: KParams::cmf_guide1): per row, the first entry above b / CMF_GUIDE1 for every bucket b
@@ -179,7 +169,7 @@ int Context::install_subspace(const spcbpt_tree_node* et, int ne, const spcbpt_t
                     guide[(size_t)e * CMF_GUIDE1 + b] = (uint16_t)k;
                 }
             }
-            if (!d_guide1) HIP_TRY(this, dev_alloc(&d_guide1, guide.size()));
+            HIP_TRY(this, d_guide1.reserve(guide.size()));
             HIP_TRY(this, hipMemcpy(d_guide1, guide.data(), guide.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
         gamma_monotone = true;   // counting equals bisecting only on a non-decreasing row that ends above every random number
@@ -264,18 +254,9 @@ int Context::set_light_trace(const spcbpt_light_trace_params& p) {
     if (begin < 0 || count < 1 || begin + count > p.num_core) { error = "set_light_trace: core range out of bounds"; return SPCBPT_ERR_INVALID_ARG; }
     lt = p;
     lt.core_count = count;
-    const size_t slots = (size_t)count * p.core_padding;
-    if (slots > scratch_capacity) {
-        dev_free(d_scratch);
-        HIP_TRY(this, dev_alloc(&d_scratch, slots));
-        scratch_capacity = slots;
-    }
-    if ((size_t)count + 1 > counts_capacity) {
-        dev_free(d_core_counts); dev_free(d_core_offsets);
-        HIP_TRY(this, dev_alloc(&d_core_counts, (size_t)count + 1));
-        HIP_TRY(this, dev_alloc(&d_core_offsets, (size_t)count + 1));
-        counts_capacity = (size_t)count + 1;
-    }
+    HIP_TRY(this, lanes[0].scratch.reserve((size_t)count * p.core_padding));
+    HIP_TRY(this, lanes[0].core_counts.reserve((size_t)count + 1));
+    HIP_TRY(this, lanes[0].core_offsets.reserve((size_t)count + 1));
     // the compact LVC holds the whole job's cache (every rank's shard after an all-gather): sized by hand, or from a probe pass
     // at the next light pass (context.h: lvc_capacity)
     if (lvc_fixed) return ensure_lvc_capacity(lvc_fixed);
@@ -288,31 +269,16 @@ int Context::probe_lvc_capacity() {
     lvc_probe_needed = false;
     const size_t worst = (size_t)lt.num_core * lt.core_padding;
     if (sync_all()) return SPCBPT_ERR_HIP;
-    kp.num_core = lt.num_core; kp.core_padding = lt.core_padding; kp.m_per_core = lt.m_per_core;
-    kp.core_begin = lt.core_begin; kp.core_count = lt.core_count; kp.launch_frame = 0x7f000001u;
-    kp.n_lframes = 0;
-    kp.lt_decorrelate = lt.decorrelate_bsdf_stream;
-    kp.lvc_scratch = d_scratch; kp.core_counts = d_core_counts;
-    {
-        const int entries = spill_entries_needed();
-        kp.spill_entries = entries;
-        const size_t need = (((size_t)lt.core_count + 255) / 256 * 256) * (size_t)entries;
-        if (entries == 0) kp.spill = nullptr;
-        else {
-            if (need > spill_capacity) { dev_free(d_spill); HIP_TRY(this, dev_alloc(&d_spill, need)); spill_capacity = need; }
-            kp.spill = d_spill;
-        }
-    }
-    kp.counters = nullptr;
-    HIP_TRY(this, hipMemsetAsync(d_core_counts, 0, ((size_t)lt.core_count + 1) * sizeof(int), stream));
+    LightLane& L = lanes[0];
+    if (int rc = light_pass_params(0x7f000001u, 0, L.scratch, L.core_counts, false, L.spill, 0)) return rc;
+    HIP_TRY(this, hipMemsetAsync(L.core_counts, 0, ((size_t)lt.core_count + 1) * sizeof(int), stream));
     kp.path_counter = d_set_counts_all + 2 * kMaxSets;   // a spare word behind the sets' counts
-    kp.work_counter = d_work_counter + kMaxRender;
+    kp.work_counter = L.work_counter;
     HIP_TRY(this, hipMemsetAsync(kp.work_counter, 0, sizeof(uint32_t), stream));
-    if (light_blocks < 0) { const char* lb = getenv("SPCBPT_LIGHT_BLOCKS"); light_blocks = lb ? std::max(1, atoi(lb)) : std::max(1, num_cus); }
     launch_light_trace(kp, tree_has_direction ? 1 : 0, light_blocks, stream);
     HIP_TRY(this, hipGetLastError());
     std::vector<int> h((size_t)lt.core_count);
-    HIP_TRY(this, hipMemcpyAsync(h.data(), d_core_counts, h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(this, hipMemcpyAsync(h.data(), L.core_counts, h.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(this, hipStreamSynchronize(stream));
     double total = 0.0;
     for (int v : h) total += (double)v;
@@ -332,10 +298,13 @@ int Context::ensure_lvc_capacity(size_t n) {
     // uncalibrated worst case core_count x padding (5.2 M) is 1.06 GB per set -- INTEGRATION.md section 4 tells hosts to calibrate.
     // The old buffers are gone from here on; if an allocation below fails the context is left EMPTY and consistent (capacity 0, every
     // pointer null, no sampler): the failed call returns SPCBPT_ERR_HIP, and a later call with a size the device can hold succeeds.
-    dev_free(d_keys); dev_free(d_keys2); dev_free(d_vals); dev_free(d_weights);
-    dev_free(d_wsorted); dev_free(d_prefix);
-    for (int s = 0; s < n_sets; s++) { dev_free(set_lvc[s]); dev_free(set_lvc_sorted[s]); dev_free(set_vals2[s]); dev_free(set_cmfs[s]); dev_free(set_guide[s]); }
-    for (int s2 = 0; s2 < kMaxSets; s2++) { set_count_host[s2] = -1; light_counts_valid[s2] = false; set_bound[s2] = -1; ev_exch_set[s2] = false; }   // the sets are empty again
+    LightLane& L = lanes[0];
+    auto release_all = [&]() {
+        L.keys.release(); d_keys2.release(); L.vals.release(); L.weights.release(); d_wsorted.release(); d_prefix.release();
+        for (int s = 0; s < n_sets; s++) { CacheSet& S = sets[s]; S.lvc.release(); S.lvc_sorted.release(); S.jump.release(); S.cmfs.release(); S.guide.release(); }
+    };
+    release_all();
+    for (CacheSet& S : sets) { S.count_host = -1; S.light_counts_valid = false; S.bound = -1; S.exch.set = false; }   // the sets are empty again
     pending.clear();
     built_sets.clear();   // samplers built in the old allocations went with them
     free_batch_build_scratch();
@@ -348,59 +317,46 @@ int Context::ensure_lvc_capacity(size_t n) {
         if (n > (size_t)strtoull(lim, nullptr, 10)) e = hipErrorOutOfMemory;
     }
     for (int s = 0; s < n_sets && e == hipSuccess; s++) {   // what the eye pass reads exists once per frame in flight (see context.h)
-        e = dev_alloc(&set_lvc[s], n);
-        if (e == hipSuccess) e = dev_alloc(&set_lvc_sorted[s], n);
-        if (e == hipSuccess) e = dev_alloc(&set_vals2[s], n);
-        if (e == hipSuccess) e = dev_alloc(&set_cmfs[s], n + 8);   // (the eye kernel reads a CMF in aligned windows of eight: kernels.hip guide_window)
-        if (e == hipSuccess) e = dev_alloc(&set_guide[s], n);
+        CacheSet& S = sets[s];
+        e = S.lvc.reserve(n);
+        if (e == hipSuccess) e = S.lvc_sorted.reserve(n);
+        if (e == hipSuccess) e = S.jump.reserve(n);
+        if (e == hipSuccess) e = S.cmfs.reserve(n + 8);   // (the eye kernel reads a CMF in aligned windows of eight: kernels.hip guide_window)
+        if (e == hipSuccess) e = S.guide.reserve(n);
     }
-    if (e == hipSuccess) e = dev_alloc(&d_keys, n);
-    if (e == hipSuccess) e = dev_alloc(&d_keys2, n);
-    if (e == hipSuccess) e = dev_alloc(&d_vals, n);
-    if (e == hipSuccess) e = dev_alloc(&d_weights, n);
-    if (e == hipSuccess) e = dev_alloc(&d_wsorted, n);
-    if (e == hipSuccess) e = dev_alloc(&d_prefix, n);
+    if (e == hipSuccess) e = L.keys.reserve(n);
+    if (e == hipSuccess) e = d_keys2.reserve(n);
+    if (e == hipSuccess) e = L.vals.reserve(n);
+    if (e == hipSuccess) e = L.weights.reserve(n);
+    if (e == hipSuccess) e = d_wsorted.reserve(n);
+    if (e == hipSuccess) e = d_prefix.reserve(n);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        dev_free(d_keys); dev_free(d_keys2); dev_free(d_vals); dev_free(d_weights); dev_free(d_wsorted); dev_free(d_prefix);
-        for (int s = 0; s < n_sets; s++) { dev_free(set_lvc[s]); dev_free(set_lvc_sorted[s]); dev_free(set_vals2[s]); dev_free(set_cmfs[s]); dev_free(set_guide[s]); }
-        select_set(lset);
+        release_all();
         error = std::string("light-vertex cache of ") + std::to_string(n) + " vertices x " + std::to_string(n_sets) + " buffer sets: " + hipGetErrorString(e) +
                 " (the context now holds NO cache: call spcbpt_lvc_set_capacity / spcbpt_lvc_calibrate with a size the device can hold)";
         return SPCBPT_ERR_HIP;
     }
-    select_set(lset);
     lvc_capacity = n;
     return 0;
 }
 
 int Context::ensure_temp(size_t bytes) {
-    if (bytes <= temp_capacity) return 0;
-    dev_free(d_temp);
-    HIP_TRY(this, dev_alloc(&d_temp, bytes));
-    temp_capacity = bytes;
+    HIP_TRY(this, lanes[0].temp.reserve(bytes));
     return 0;
 }
 
 int Context::ensure_lane_b() {
-    if (!lstream_b) {
+    LightLane& B = lanes[1];
+    if (!B.stream) {
         int least = 0, greatest = 0;
         HIP_TRY(this, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(this, hipStreamCreateWithPriority(&lstream_b, hipStreamNonBlocking, greatest));
+        HIP_TRY(this, hipStreamCreateWithPriority(&B.stream, hipStreamNonBlocking, greatest));
     }
-    const size_t slots = (size_t)lt.core_count * lt.core_padding;
-    if (slots > b_scratch_capacity) { dev_free(b_scratch); HIP_TRY(this, dev_alloc(&b_scratch, slots)); b_scratch_capacity = slots; }
-    if ((size_t)lt.core_count + 1 > b_counts_capacity) {
-        dev_free(b_core_counts); dev_free(b_core_offsets);
-        HIP_TRY(this, dev_alloc(&b_core_counts, (size_t)lt.core_count + 1));
-        HIP_TRY(this, dev_alloc(&b_core_offsets, (size_t)lt.core_count + 1));
-        b_counts_capacity = (size_t)lt.core_count + 1;
-    }
-    if (lvc_capacity > b_keys_capacity) {
-        dev_free(b_keys); dev_free(b_vals); dev_free(b_weights);
-        HIP_TRY(this, dev_alloc(&b_keys, lvc_capacity)); HIP_TRY(this, dev_alloc(&b_vals, lvc_capacity)); HIP_TRY(this, dev_alloc(&b_weights, lvc_capacity));
-        b_keys_capacity = lvc_capacity;
-    }
+    HIP_TRY(this, B.scratch.reserve((size_t)lt.core_count * lt.core_padding));
+    HIP_TRY(this, B.core_counts.reserve((size_t)lt.core_count + 1));
+    HIP_TRY(this, B.core_offsets.reserve((size_t)lt.core_count + 1));
+    HIP_TRY(this, B.keys.reserve(lvc_capacity)); HIP_TRY(this, B.vals.reserve(lvc_capacity)); HIP_TRY(this, B.weights.reserve(lvc_capacity));
     return 0;
 }
 
@@ -423,7 +379,7 @@ int Context::install_minimal_tuple() {
         rc = fetch_counts();
         if (rc) return rc;
         host.resize(lvc_count);
-        HIP_TRY(this, hipMemcpy(host.data(), d_lvc, (size_t)lvc_count * sizeof(LightVertex), hipMemcpyDeviceToHost));
+        HIP_TRY(this, hipMemcpy(host.data(), sets[lset].lvc, (size_t)lvc_count * sizeof(LightVertex), hipMemcpyDeviceToHost));
         for (const auto& v : host) {
             float w = (v.flux[0] + v.flux[1] + v.flux[2]) / v.pdf;
             if (std::isnan(w) || std::isinf(w)) w = 0;
@@ -443,39 +399,27 @@ int Context::install_minimal_tuple() {
     return install_subspace(&leaf, 1, &leaf, 1, q.data(), g.data());
 }
 
+// Every DevBuf member frees itself after this body, on a device spcbpt_destroy has synchronised; what is left here is what is no
+// DevBuf, in the order it needs: spans and preprocessing state first, streams before the events recorded on them.
 Context::~Context() {
     resolve_spans();
     free_preprocess();
-    dev_free(d_nodes); dev_free(d_nodes_q); dev_free(d_nodes_q2); dev_free(d_tris); dev_free(d_tri_orig); dev_free(d_mats); dev_free(d_lights); dev_free(d_tex);
+    dev_free(d_lights); dev_free(d_env_tex); dev_free(d_env_cmf); dev_free(d_eye_tree); dev_free(d_light_tree);
     for (auto p : d_tex_data) (void)hipFree(p);
-    dev_free(d_env_tex); dev_free(d_env_cmf); dev_free(d_accum); dev_free(d_frame); dev_free(d_eye_tree); dev_free(d_light_tree); dev_free(d_Q); dev_free(d_gamma); dev_free(d_gamma2); dev_free(d_guide1); dev_free(d_gamma_q);
-    dev_free(d_scratch); dev_free(d_core_counts); dev_free(d_core_offsets); dev_free(d_keys); dev_free(d_keys2);
-    dev_free(d_vals); dev_free(d_weights); dev_free(d_wsorted); dev_free(d_prefix);
-    for (int s = 0; s < kMaxSets; s++) { dev_free(set_lvc[s]); dev_free(set_lvc_sorted[s]); dev_free(set_vals2[s]); dev_free(set_cmfs[s]); dev_free(set_guide[s]); dev_free(set_subspace[s]); }
-    dev_free(d_set_counts_all); dev_free(lb_scratch); dev_free(lb_core_counts); dev_free(lb_core_offsets); dev_free(lb_path_counts); dev_free(lb_spill);
-    dev_free(d_counters); dev_free(d_diag); dev_free(d_work_counter); if (h_import_counts) (void)hipHostFree(h_import_counts); if (h_light_counts) (void)hipHostFree(h_light_counts);
-    for (int s2 = 0; s2 < kMaxRender; s2++) { for (int k = 0; k < kMaxBatchFrames; k++) dev_free(d_result_b[s2][k]); if (d_frames[s2]) (void)hipFree(d_frames[s2]); }
+    if (h_import_counts) (void)hipHostFree(h_import_counts);
+    if (h_light_counts) (void)hipHostFree(h_light_counts);
     if (h_frames) (void)hipHostFree(h_frames);
-    for (int g2 = 0; g2 < 2; g2++) if (ev_import[g2]) (void)hipEventDestroy(ev_import[g2]);
-    for (int s2 = 0; s2 < kMaxRender; s2++) for (int g2 = 0; g2 < kDescRing; g2++) if (ev_desc[s2][g2]) (void)hipEventDestroy(ev_desc[s2][g2]);
-    dev_free(b_scratch); dev_free(b_core_counts); dev_free(b_core_offsets); dev_free(b_keys); dev_free(b_vals); dev_free(b_weights); dev_free(b_temp); dev_free(b_spill);
-    if (lstream_b) (void)hipStreamDestroy(lstream_b); dev_free(d_spill); dev_free(d_temp); dev_free(d_hist);
-    dev_free(sbb_keys); dev_free(sbb_weights); dev_free(sbb_wsorted); dev_free(sbb_hist);
-    for (int s = 0; s < kMaxRender; s++) {
-        if (rstreams[s] && rstreams[s] != stream) (void)hipStreamDestroy(rstreams[s]);
-        if (ev_merge[s]) (void)hipEventDestroy(ev_merge[s]);
-        dev_free(d_result[s]); dev_free(d_spill_rs[s]); dev_free(d_splat[s]);
+    for (hipEvent_t ev : ev_import) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ring : ev_desc) for (hipEvent_t ev : ring) if (ev) (void)hipEventDestroy(ev);
+    if (lanes[1].stream) (void)hipStreamDestroy(lanes[1].stream);
+    for (int k = 0; k < kMaxRender; k++) {
+        if (rstreams[k] && rstreams[k] != stream) (void)hipStreamDestroy(rstreams[k]);
+        if (ev_merge[k].ev) (void)hipEventDestroy(ev_merge[k].ev);
     }
-    free_features();
     if (cstream) (void)hipStreamDestroy(cstream);
     if (stream) (void)hipStreamDestroy(stream);
-    for (int s = 0; s < kMaxSets; s++) {
-        if (ev_sampler[s]) (void)hipEventDestroy(ev_sampler[s]);
-        if (ev_render[s]) (void)hipEventDestroy(ev_render[s]);
-        if (ev_light[s]) (void)hipEventDestroy(ev_light[s]);
-        if (ev_set_stream[s]) (void)hipEventDestroy(ev_set_stream[s]);
-        if (ev_exch[s]) (void)hipEventDestroy(ev_exch[s]);
-    }
+    for (CacheSet& S : sets)
+        for (Event* e : {&S.sampler, &S.render, &S.light, &S.on_stream, &S.exch}) if (e->ev) (void)hipEventDestroy(e->ev);
 }
 
 }  // namespace spc

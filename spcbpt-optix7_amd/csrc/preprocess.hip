@@ -86,8 +86,8 @@ int Context::preprocess_stage(int stage, int arg) {
                 rc = fetch_counts();
                 if (rc) return rc;
                 keys.resize(lvc_count); w.resize(lvc_count);
-                HIP_TRY_P(hipMemcpy(keys.data(), d_keys, (size_t)lvc_count * 4, hipMemcpyDeviceToHost));
-                HIP_TRY_P(hipMemcpy(w.data(), d_weights, (size_t)lvc_count * 4, hipMemcpyDeviceToHost));
+                HIP_TRY_P(hipMemcpy(keys.data(), lanes[0].keys, (size_t)lvc_count * 4, hipMemcpyDeviceToHost));
+                HIP_TRY_P(hipMemcpy(w.data(), lanes[0].weights, (size_t)lvc_count * 4, hipMemcpyDeviceToHost));
                 if (path_count <= 0) { error = "stage 2: a light pass produced no paths"; return SPCBPT_ERR_STATE; }
                 P.accumulate_q(keys.data(), w.data(), lvc_count, path_count);
             }

@@ -293,3 +293,49 @@ def test_cache_sets_are_sized_from_a_probe_pass_and_an_overflow_is_reported(gpu,
     r2.sync()
     assert np.array_equal(r2.read_accum(), want)
     assert r2.lvc_capacity()[0] == n + n // 4
+
+
+def _ahead(r, frames):
+    """`frames` frames in light-ahead order: every pass is launched one frame before its sampler is built."""
+    r.launch("light trace", 1)
+    for f in range(frames):
+        r.launch("light trace", f + 2)
+        r.build_sampler()
+        r.launch("SPCBPT_eye", f)
+
+
+def test_a_small_ring_comes_round_on_both_lanes(gpu, pkg, monkeypatch):
+    """Single passes in light-ahead mode alternate between the two light lanes; with four buffer sets and nine frames every set is
+    rewritten at least twice, by either lane, while eye kernels of earlier frames are still in flight.  The film is the plain order's."""
+    plain = _renderer(pkg)                # the plain order over the same nine frames, before the environment is touched
+    for f in range(9):
+        plain.launch("light trace", f + 1); plain.build_sampler(); plain.launch("SPCBPT_eye", f)
+    plain.sync()
+    want = plain.read_accum().copy()
+    monkeypatch.setenv("SPCBPT_SETS", "4")
+    r = _renderer(pkg)
+    assert r.lvc_capacity()[1] == 4
+    r.set_light_ahead(True)
+    _ahead(r, 9)
+    r.sync()
+    assert np.array_equal(r.read_accum(), want)
+
+
+def test_light_geometry_regrown_after_the_second_lane_exists(gpu, pkg):
+    """A larger light-pass geometry set while the second lane's buffers exist at the old size and a pass is still queued: every lane
+    buffer regrows, the set capacity is probed again, and the frames are those of a context that had the geometry from the start."""
+    a = _renderer(pkg)
+    a.set_light_ahead(True)
+    _ahead(a, 2)                         # the second lane now holds buffers for 3000 cores
+    a.sync()
+    a.set_light_trace(6000, 64, 1)
+    a.clear_accum()
+    _ahead(a, 3)
+    a.sync()
+    b = _renderer(pkg)
+    b.set_light_trace(6000, 64, 1)
+    for f in range(3):
+        b.launch("light trace", f + 1); b.build_sampler(); b.launch("SPCBPT_eye", f)
+    b.sync()
+    assert np.array_equal(a.read_accum(), b.read_accum())
+    assert a.pipeline_state()["pending_passes"] == 1      # the pass launched ahead, nothing left over from the old geometry
