@@ -372,7 +372,11 @@ int spcbpt_image_size(spcbpt_ctx* ctx, int* width, int* height);
  * sky by next-event estimation and shows it to primary rays (hit_program.cu:502-518, raygen.cu:687-697).  As upstream, an eye
  * SUB-PATH that leaves the scene sees nothing by default: spcbpt_set_environment_mode below opts in.  center / radius = sky.center / sky.r (upstream: centre and diagonal of the scene
  * box it computes); radius <= 0 or center == NULL: centre and diagonal of the true bounding box.  The quad lights'
- * patch subspaces move up by 100 (their div_level^2 may sum to 100 at most).  Call once, before the first light pass. */
+ * patch subspaces move up by 100 (their div_level^2 may sum to 100 at most).  Call once, before the first light pass.
+ * Refused with SPCBPT_ERR_INVALID_ARG (the context stays as it was): more than 2^26 texels, a non-finite texel, an image without
+ * energy, and a map too large for the float sampling table -- the table is accumulated in float as upstream's, and once an entry
+ * does not exceed the one before it that texel would never be drawn although it shines (next-event estimation would lose its light);
+ * the message names the first such texel.  (A smooth 2048 x 1024 sky still builds; a 4096 x 2048 one loses 1.4 % of its texels.) */
 int spcbpt_set_environment(spcbpt_ctx* ctx, const float* rgba, int width, int height, const float* center, float radius);
 int spcbpt_get_environment(spcbpt_ctx* ctx, int* width, int* height, float center[3], float* radius, int* n_lights);
 /* Opt-in corrections of the sky's strategies (default 0 = upstream's behaviour); flags take effect only while the context has an
@@ -539,7 +543,16 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *                        csrc/second_stage_guided.inc.h, the text both compile); STAGE2 above is the reference's bisection.
  *   SPCBPT_UNIT_SORTED   in 1: place i in the sorted cache (i >= vertex count: zeros)   out 24: the 96 bytes of record i
  *                        (spcbpt_light_vertex), = the cache's record jump[i]
- * STAGE2, UNIFORM, STAGE2_GUIDED and SORTED need a built sampler (else SPCBPT_ERR_STATE).
+ *   SPCBPT_UNIT_ENV      in 4: direction3 (as given: not normalised), seed
+ *                        out 24: dir2uv(direction) u, v; env_color3, env_pdf (per solid angle, not yet divided by the light count),
+ *                        env_label of the direction; env_sample(seed)3, seed'; then everything env_light_sample returns for the
+ *                        SAME starting seed: position3, emission3, normal3, pdf (divided by the light count), subspace, dir_pos_pdf, seed'
+ *   SPCBPT_UNIT_ENV_TABLE in 1: texel index i (>= width * height: SPCBPT_ERR_INVALID_ARG)
+ *                        out 5: the sampling CMF's entry i (over the raster as read), the four floats of texel i of the row-flipped texture
+ *   SPCBPT_UNIT_TEX      in 3: texture number as spcbpt_material::albedo_tex counts it (1 .. n_textures, else SPCBPT_ERR_INVALID_ARG), u, v
+ *                        out 6: tex_fetch_rgb3 (bilinear, wrap), the linearised colour3 a hit stores (powf(., 2.2f))
+ * STAGE2, UNIFORM, STAGE2_GUIDED and SORTED need a built sampler, ENV and ENV_TABLE an environment map (else SPCBPT_ERR_STATE);
+ * BSDF, BSEARCH, ENV, ENV_TABLE and TEX run without a subspace tuple.
  * The ray of EYE_STEP starts at the last vertex's position.  Host pointers; returns after the kernel has run. */
 typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-path vertex carries (BDPTVertex.h:9-70) */
     float position[3], normal[3], flux[3], color[3], last_position[3], rmis3[3];
@@ -548,7 +561,8 @@ typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-pa
 } spcbpt_unit_eye_vertex;
 enum spcbpt_unit_op { SPCBPT_UNIT_BSDF = 0, SPCBPT_UNIT_TREE = 1, SPCBPT_UNIT_STAGE1 = 2, SPCBPT_UNIT_BSEARCH = 3, SPCBPT_UNIT_STAGE2 = 4,
                       SPCBPT_UNIT_UNIFORM = 5, SPCBPT_UNIT_CONNECT = 6, SPCBPT_UNIT_EYE_STEP = 7, SPCBPT_UNIT_SKY_MISS = 8,
-                      SPCBPT_UNIT_STAGE2_GUIDED = 9, SPCBPT_UNIT_SORTED = 10 };
+                      SPCBPT_UNIT_STAGE2_GUIDED = 9, SPCBPT_UNIT_SORTED = 10, SPCBPT_UNIT_ENV = 11, SPCBPT_UNIT_ENV_TABLE = 12,
+                      SPCBPT_UNIT_TEX = 13 };
 int spcbpt_debug_unit(spcbpt_ctx* ctx, int op, const uint32_t* in, int in_words, uint32_t* out, int out_words, int n,
                       const float* aux, int aux_floats);
 

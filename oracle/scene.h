@@ -42,7 +42,7 @@ inline float3 uv2dir(float2 uv) {
 }
 inline float2 dir2uv(float3 dir) {
     float theta = atan2f(dir.x, dir.z);
-    float phi = M_PIf_ * 0.5f - acosf(dir.y);
+    float phi = M_PIf_ * 0.5f - acosf(fmaxf(-1.0f, fminf(dir.y, 1.0f)));   // clamped as the product's dir2uv (upstream: NaN for |y| > 1)
     float u = (theta + M_PIf_) * (0.5f * M_1_PIf_);
     float v = 0.5f * (1.0f + sinf(phi));
     return float2{u, v};

@@ -361,11 +361,16 @@ int spcbpt_debug_trace_bench(spcbpt_ctx* c, const float* rays, int n, int mode, 
 
 int spcbpt_debug_unit(spcbpt_ctx* c, int op, const uint32_t* in, int in_words, uint32_t* out, int out_words, int n, const float* aux, int aux_floats) {
     CTX_CHECK(c);
-    static const int need_in[11] = {24, 10, 2, 3, 2, 1, 52, 36, 32, 2 * SPCBPT_CONNECTION_N, 1}, need_out[11] = {12, 1, 6, 3, 5, 3, 4, 40, 6, 4 * SPCBPT_CONNECTION_N, 24};
-    if (op < 0 || op > 10 || !in || !out || n < 0 || in_words < need_in[op] || out_words < need_out[op]) { c->error = "debug_unit: bad op or record size"; return SPCBPT_ERR_INVALID_ARG; }
-    if (op != SPCBPT_UNIT_BSDF && op != SPCBPT_UNIT_BSEARCH && !c->have_subspace) { c->error = "debug_unit: needs a subspace tuple"; return SPCBPT_ERR_STATE; }
+    static const int need_in[14] = {24, 10, 2, 3, 2, 1, 52, 36, 32, 2 * SPCBPT_CONNECTION_N, 1, 4, 1, 3}, need_out[14] = {12, 1, 6, 3, 5, 3, 4, 40, 6, 4 * SPCBPT_CONNECTION_N, 24, 24, 5, 6};
+    if (op < 0 || op > 13 || !in || !out || n < 0 || in_words < need_in[op] || out_words < need_out[op]) { c->error = "debug_unit: bad op or record size"; return SPCBPT_ERR_INVALID_ARG; }
+    if (op != SPCBPT_UNIT_BSDF && op != SPCBPT_UNIT_BSEARCH && op != SPCBPT_UNIT_ENV && op != SPCBPT_UNIT_ENV_TABLE && op != SPCBPT_UNIT_TEX && !c->have_subspace) { c->error = "debug_unit: needs a subspace tuple"; return SPCBPT_ERR_STATE; }
     if ((op == SPCBPT_UNIT_STAGE2 || op == SPCBPT_UNIT_UNIFORM || op == SPCBPT_UNIT_STAGE2_GUIDED || op == SPCBPT_UNIT_SORTED) && !c->have_sampler) { c->error = "debug_unit: needs a built sampler"; return SPCBPT_ERR_STATE; }
     if (op == SPCBPT_UNIT_SKY_MISS && !c->kp.scene.env.valid) { c->error = "debug_unit: SKY_MISS needs an environment map"; return SPCBPT_ERR_STATE; }
+    if ((op == SPCBPT_UNIT_ENV || op == SPCBPT_UNIT_ENV_TABLE) && !c->kp.scene.env.valid) { c->error = "debug_unit: ENV / ENV_TABLE need an environment map"; return SPCBPT_ERR_STATE; }
+    if (op == SPCBPT_UNIT_ENV_TABLE)
+        for (int i = 0; i < n; i++) if (in[(size_t)i * in_words] >= (uint32_t)c->kp.scene.env.size) { c->error = "debug_unit: ENV_TABLE texel index out of range"; return SPCBPT_ERR_INVALID_ARG; }
+    if (op == SPCBPT_UNIT_TEX)
+        for (int i = 0; i < n; i++) if (in[(size_t)i * in_words] < 1u || in[(size_t)i * in_words] > (uint32_t)c->d_tex_data.size()) { c->error = "debug_unit: TEX texture number out of range (1 .. the scene's texture count)"; return SPCBPT_ERR_INVALID_ARG; }
     if (op == SPCBPT_UNIT_BSEARCH && (!aux || aux_floats < 1)) { c->error = "debug_unit: BSEARCH needs the CMF in aux"; return SPCBPT_ERR_INVALID_ARG; }
     if (n == 0) return SPCBPT_OK;
     if (c->sync_all()) return SPCBPT_ERR_HIP;

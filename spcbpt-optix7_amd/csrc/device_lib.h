@@ -99,9 +99,12 @@ SPC_DEV f3 uv2dir(float u, float v) {
     const float theta = (float)(u / (0.5 * 0.318309886183790671538f) - kPi);
     return mk3(cosf(phi) * sinf(theta), cosf(kPi * 0.5f - phi), cosf(phi) * cosf(theta));
 }
+// dir.y is clamped to [-1, 1] (upstream: not): bsdf_sample's specular branch returns 2 dot(V, h) h - V without renormalising, so a
+// reflection towards a pole arrives with |y| up to 1.0000008, whose acosf is NaN -- and the NaN went through the bilinear weights
+// into the film.  Directions of unit length or less keep their bits.
 SPC_DEV void dir2uv(f3 dir, float& u, float& v) {
     const float theta = atan2f(dir.x, dir.z);
-    const float phi = kPi * 0.5f - acosf(dir.y);
+    const float phi = kPi * 0.5f - acosf(clampf(dir.y, -1.0f, 1.0f));
     u = (theta + kPi) * (0.5f * 0.318309886183790671538f);
     v = 0.5f * (1.0f + sinf(phi));
 }

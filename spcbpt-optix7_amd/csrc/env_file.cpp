@@ -131,7 +131,7 @@ void env_build(const float* raster, int w, int h, std::vector<float>& tex, std::
             float* t = &tex[((size_t)j * w + i) * 4];
             t[0] = q[0]; t[1] = q[1]; t[2] = q[2]; t[3] = 1.0f;
         }
-    // envMapCMFBuild: every texel's luminance (r + g + b) plus the mean of its up-to-12 neighbours within |dx| + |dy| <= 2,
+    // envMapCMFBuild: every texel's luminance (r + g + b) plus the mean over the cells of the diamond |dx| + |dy| <= 2 inside the image (up to 13: surroundsIndex keeps the texel itself),
     // accumulated in float over the raster AS READ (not flipped: as written), normalised, 25 % uniform mixed in
     cmf.assign((size_t)size, 0.0f);
     const float uniform_rate = 0.25f;
@@ -156,6 +156,14 @@ void env_build(const float* raster, int w, int h, std::vector<float>& tex, std::
         cmf[i] /= sum;
         cmf[i] = cmf[i] * (1 - uniform_rate) + (uniform_pdf * (i + 1) * uniform_rate);
     }
+}
+
+
+long long env_first_undrawable(const std::vector<float>& cmf) {
+    if (!cmf.empty() && !(cmf[0] > 0.0f)) return 0;
+    for (size_t i = 1; i < cmf.size(); i++)
+        if (!(cmf[i] > cmf[i - 1])) return (long long)i;
+    return -1;
 }
 
 }  // namespace spc

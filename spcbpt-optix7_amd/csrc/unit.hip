@@ -15,6 +15,10 @@
 //   EYE_STEP  traceEyeSubPath + __closesthit__eyeSubpath / _LightSource + rmis::light_hit + lightStraghtHit
 //             (cuProg.h:434-461, hit_program.cu:62-147, 246-340, rmis.h:359-389, raygen.cu:305-317)
 //   SKY_MISS  an escaped eye path that sees the sky: eye_sky_miss = rmis::light_hit_env (rmis.h:325-358), corrected sign (eye_walk.h)
+//   ENV       the environment map as a light, function by function: dir2uv, envInfo_device::color / pdf / getLabel / sample and
+//             lightSample's ENV branch (optixPathTracer.h:139-165, cuProg.h:125-243, 611-666)
+//   ENV_TABLE one entry of the sky's device tables (sampling CMF, row-flipped texture): how tests read them
+//   TEX       ColorTexSample's fetch and linearisation (hit_program.cu:182-198, cuProg.h:361-368) at a caller-supplied (u, v)
 #include <hip/hip_runtime.h>
 
 #include "device_lib.h"
@@ -188,6 +192,32 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
         int label = -1;
         stw3(o, eye_sky_miss(p, w.dir, last.depth == 0, last, w, cn, &wgt, &label));
         stf(o + 3, wgt); o[4] = (uint32_t)label; o[5] = 0u;
+        break;
+    }
+    case SPCBPT_UNIT_ENV: {
+        const DEnv& E = p.scene.env;
+        const f3 dir = ldw3(r);
+        float u, v;
+        dir2uv(dir, u, v);
+        stf(o, u); stf(o + 1, v);
+        stw3(o + 2, env_color(E, dir)); stf(o + 5, env_pdf(E, dir)); o[6] = (uint32_t)env_label(E, dir);
+        uint32_t s1 = r[3], s2 = r[3];
+        stw3(o + 7, env_sample(E, s1)); o[10] = s1;
+        float dir_pos_pdf = 0.0f;
+        const LightSampleD ls = env_light_sample(p.scene, s2, dir_pos_pdf);
+        stw3(o + 11, ls.position); stw3(o + 14, ls.emission); stw3(o + 17, ls.normal); stf(o + 20, ls.pdf); o[21] = (uint32_t)ls.subspace;
+        stf(o + 22, dir_pos_pdf); o[23] = s2;
+        break;
+    }
+    case SPCBPT_UNIT_ENV_TABLE: {   // (the host has checked the index against the table's size)
+        const DEnv& E = p.scene.env;
+        const float4 t = ldq(E.tex, r[0]);
+        stf(o, E.cmf[r[0]]); stf(o + 1, t.x); stf(o + 2, t.y); stf(o + 3, t.z); stf(o + 4, t.w);
+        break;
+    }
+    case SPCBPT_UNIT_TEX: {         // (the host has checked the texture number: 1 .. the scene's texture count, as Pbr::albedo_tex counts)
+        const f3 t = tex_fetch_rgb(p.scene.tex[r[0] - 1], ldf(r + 1), ldf(r + 2));
+        stw3(o, t); stw3(o + 3, mk3(powf(t.x, 2.2f), powf(t.y, 2.2f), powf(t.z, 2.2f)));   // color_tex_sample's linearisation
         break;
     }
     default: break;
