@@ -83,6 +83,11 @@ def test_light_vertex_cache_matches_oracle(gpu, pkg, ob, lt):
 
 
 def check_lvc(pkg, ob, scene, lt):
+    """The device's cache against the oracle's at the same seeds: the same (path_id, depth) sequence and the oracle's VALUES on the
+    common prefix up to the first Russian-roulette / tie flip (at least half of the cache), at the 99th percentile.  That the walk draws
+    the oracle's random numbers and lands where the oracle lands is only held here.  What every single record holds -- each field
+    recomputed in float64 from the record stored before it, behind the first flip too, with a hard bar on every record -- is the audit of
+    tests/test_gpu_lvc_audit.py."""
     r, o = _pair(pkg, ob, scene, 8, 8, lt=lt)
     tup = minimal_tuple(o, 2)
     r.set_subspace(*tup); o.set_subspace(*tup)
