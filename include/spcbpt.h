@@ -478,6 +478,72 @@ int spcbpt_denoise_host(const float* accum_rgba, const float* albedo_rgba, const
                         const float eye[3], const float U[3], const float V[3], const float W[3],
                         int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
 
+/* Second moment of the film (no reference counterpart), opt-in: spcbpt_set_film_moments(ctx, 1).  Off (the default) a context keeps
+ * its footprint, its launches and its film bits.  On, the context keeps one float4-per-pixel plane in the film's row order,
+ *   m2n(p) = (M2_r, M2_g, M2_b, n),
+ * and every film merge of spcbpt_launch ("pt", "SPCBPT_eye", "SPCBPT_no_rmis", "lt") and of spcbpt_merge_deferred(ctx, 1) is preceded
+ * on its stream by an update of the pixels it is about to rewrite (the rows of the launch's 8-row bands), from the frame's sample x
+ * and the mean before the merge, accum:
+ *   subframe == 0:  M2 = 0, n = 1                                   (the film overwrites on subframe 0, so the moments restart)
+ *   subframe  > 0:  a = 1 / (float)(subframe + 1),  mean' = mean + a (x - mean)   (the float operations of the merge: mean' is bit
+ *                   M2 += (x - mean) (x - mean') per channel,  n += 1              for bit what the merge is about to store)
+ * With subframes 0, 1, 2, ... in order this is Welford's update -- the assumption the film's own running mean makes; switched on
+ * in mid-film, n counts the merges since.  A dropped deferred frame updates nothing.  The variance of the mean of channel k is
+ * M2_k / (n (n - 1)) for n >= 2.  The plane (16 B per pixel) is allocated and zeroed at the first merge after spcbpt_resize, freed
+ * by spcbpt_resize and by switching off (which waits for the context's streams), zeroed by spcbpt_clear_accum.  While the switch is on
+ * spcbpt_launch_eye_batch returns SPCBPT_ERR_STATE (its merge takes up to 32 frames per pixel in one pass and keeps no moments);
+ * the N-GPU host (spcbpt_mgpu.h) and the viewer do not use the switch.  The kernel-time span of the updates is "moments". */
+int spcbpt_set_film_moments(spcbpt_ctx* ctx, int enabled);
+int spcbpt_get_film_moments(spcbpt_ctx* ctx, int* enabled);
+/* Host copy of the plane (zeros before the first merge); waits like spcbpt_read_accum.  SPCBPT_ERR_STATE while the switch is off. */
+int spcbpt_read_film_moments(spcbpt_ctx* ctx, float* m2n_out);
+/* One update of n_pixels pixels on the host: the per-pixel function the kernel runs (float32, no contraction) on float4-per-pixel
+ * arrays -- the film before the merge, the frame's samples, and the plane, updated in place.  No context and no GPU needed.
+ * SPCBPT_ERR_INVALID_ARG for a NULL pointer or n_pixels outside 1 .. 2^28. */
+int spcbpt_film_moments_update_host(const float* mean_before_rgba, const float* sample_rgba, uint32_t subframe, int64_t n_pixels,
+                                    float* m2n_inout);
+
+/* Film error: how converged the film is.  The relative standard error of a pixel with n >= 2,
+ *   e(p) = (0.3 sd_r + 0.6 sd_g + 0.1 sd_b) / (1e-2 + L(accum(p))),   sd_k = sqrt(max(M2_k, 0) / (n (n - 1))),   L = 0.3 r + 0.6 g + 0.1 b
+ * -- the channels taken as fully correlated (an upper bound), the film's luminance weights, the denoiser's floor of 1e-2 -- reduced
+ * over the pixels with n >= 2: their number, the mean and the maximum of e (pixels == 0: mean = max = 0).  Per-pixel terms in
+ * float32, summed in double; per wave a fixed shuffle tree, per block through LDS, the blocks' partials added in index order by a
+ * second one-block launch: no atomics, so two calls on the same film return the same bits.  Waits for the merges queued so far
+ * and reads 24 bytes back.  SPCBPT_ERR_STATE while the moments are off.  The kernel-time span is "film_error". */
+typedef struct spcbpt_film_error_stats {
+    int64_t pixels;
+    double mean, max;
+} spcbpt_film_error_stats;
+int spcbpt_film_error_struct_size(void);   /* sizeof(spcbpt_film_error_stats) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+int spcbpt_film_error(spcbpt_ctx* ctx, spcbpt_film_error_stats* out);
+/* The same over caller arrays on the host (float4 per pixel each), pixels in index order.  SPCBPT_ERR_INVALID_ARG as above. */
+int spcbpt_film_error_host(const float* accum_rgba, const float* m2n, int64_t n_pixels, spcbpt_film_error_stats* out);
+
+/* Variance-guided a-trous denoiser: the pipeline, guides, buffers and outputs of spcbpt_denoise (read with spcbpt_read_denoised),
+ * with a colour weight measured in the pixel's own standard error instead of a fixed relative width -- so the filter narrows as
+ * the film converges and becomes the identity in the limit, where spcbpt_denoise blurs a 4-frame and a 4000-frame film alike.
+ * A scalar variance v of the demodulated luminance travels with c.  Start values (w = (0.3, 0.6, 0.1), sd_k as above):
+ *   c_0(p) = accum(p).rgb / max(albedo(p).rgb, 1e-3)
+ *   v_0(p) = (sum_k w_k sd_k / max(albedo_k(p), 1e-3))^2     for n(p) >= 2
+ *          = L(c_0(p))^2                                     for n(p) <  2   (unknown variance: as uncertain as its own value)
+ * Iteration i with step s = 2^i, taps q = p + s (a, b) inside the image, k = (1, 4, 6, 4, 1) / 16:
+ *   v~_i(p) = the (1/4, 1/2, 1/4)^2 mean of v_i over the 3 x 3 neighbours of p at distance 1 inside the image, renormalised
+ *   w(p, q) = k[a] k[b] exp(- (L(c_i(q)) - L(c_i(p)))^2 / (sigma_v^2 v~_i(p) + (1e-3 (1e-2 + L(c_i(p))))^2)
+ *                           - |n(q) - n(p)|^2 / sigma_n^2  -  |X(q) - X(p)|^2 / (sigma_x s)^2)
+ *   c_{i+1}(p) = sum_q w c_i(q) / sum_q w,      v_{i+1}(p) = sum_q w^2 v_i(q) / (sum_q w)^2
+ * Smooth weights only; the single branch is on the integer n.  A pixel of zero variance merges only with neighbours within a
+ * thousandth of its luminance; the centre tap keeps the sum non-empty.  spcbpt_denoise_params is reused: its sigma_c field is read
+ * as sigma_v (<= 0: SPCBPT_DENOISE_SIGMA_V = 4, the one value of {2, 4, 8} that leaves the Cornell box closer to the converged image
+ * than the film at 4 and at 64 frames: DESIGN.md 8e; tools/denoise_grid.py), sigma_n and sigma_x as in spcbpt_denoise.  Needs the moments switched on, a feature launch since the
+ * last spcbpt_resize and no deferred frame outstanding (else SPCBPT_ERR_STATE, with text).  Asynchronous; the kernel-time span is
+ * "denoise_variance". */
+#define SPCBPT_DENOISE_SIGMA_V 4.0f
+int spcbpt_denoise_variance(spcbpt_ctx* ctx, const spcbpt_denoise_params* params);
+/* The same filter on caller buffers on the host (see spcbpt_denoise_host), with the moment plane as spcbpt_read_film_moments gives it. */
+int spcbpt_denoise_variance_host(const float* accum_rgba, const float* m2n, const float* albedo_rgba, const float* normal_depth_rgba,
+                                 const float eye[3], const float U[3], const float V[3], const float W[3],
+                                 int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
+
 int spcbpt_get_counters(spcbpt_ctx* ctx, spcbpt_counters* out);
 int spcbpt_reset_counters(spcbpt_ctx* ctx);
 /* Developer aid (no reference counterpart): wave-clock totals the counting build of the "SPCBPT_eye" megakernel spent in

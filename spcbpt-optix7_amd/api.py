@@ -53,6 +53,13 @@ class DenoiseParams(C.Structure):   # spcbpt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_x", C.c_float)]
 
 
+class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
+    _fields_ = [("pixels", C.c_int64), ("mean", C.c_double), ("max", C.c_double)]
+
+    def as_dict(self):
+        return {"pixels": int(self.pixels), "mean": float(self.mean), "max": float(self.max)}
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("texcoords", C.c_void_p), ("n_vertices", C.c_int32),
                 ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("n_triangles", C.c_int32),
@@ -351,6 +358,53 @@ def denoise_host(accum, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_
     return out
 
 
+def denoise_variance_host(accum, m2n, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_v=0.0, sigma_n=0.0, sigma_x=0.0):
+    """spcbpt_denoise_variance_host: the variance-guided a-trous denoiser of Renderer.denoise_variance on (h, w, 4) float32 arrays as
+    read_accum / read_film_moments / read_features give them.  Host code in float32 -- the per-pixel function the kernels run; no GPU
+    needed.  A sigma <= 0 takes its default.  Returns the denoised (h, w, 4) image; the inputs are not written."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (accum, m2n, albedo, normal_depth)]
+    h, w = a[0].shape[:2]
+    if any(v.shape != (h, w, 4) for v in a):
+        raise SpcbptError("denoise_variance_host: accum, m2n, albedo and normal_depth must be (h, w, 4) arrays of one size")
+    cam = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W)]
+    out = np.zeros((h, w, 4), dtype=np.float32)
+    p = DenoiseParams(int(iterations), float(sigma_v), float(sigma_n), float(sigma_x))
+    rc = lib.spcbpt_denoise_variance_host(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), *[_fp(v) for v in cam], w, h, C.byref(p), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"denoise_variance_host failed ({rc})")
+    return out
+
+
+def film_moments_update_host(mean_before, sample, subframe, m2n):
+    """spcbpt_film_moments_update_host: one merge's update of the moment plane `m2n` ((..., 4) float32, C-contiguous, updated IN PLACE)
+    from the film before the merge and the frame's samples (same shape).  The per-pixel function the kernel runs; no GPU needed."""
+    lib = load_library()
+    a, x = (np.ascontiguousarray(v, dtype=np.float32) for v in (mean_before, sample))
+    if not (isinstance(m2n, np.ndarray) and m2n.dtype == np.float32 and m2n.flags["C_CONTIGUOUS"]):
+        raise SpcbptError("film_moments_update_host: m2n must be a C-contiguous float32 array (it is updated in place)")
+    if a.shape != m2n.shape or x.shape != m2n.shape or m2n.shape[-1] != 4:
+        raise SpcbptError("film_moments_update_host: mean_before, sample and m2n must be (..., 4) arrays of one shape")
+    rc = lib.spcbpt_film_moments_update_host(_fp(a), _fp(x), int(subframe), m2n.size // 4, _fp(m2n))
+    if rc != 0:
+        raise SpcbptError(f"film_moments_update_host failed ({rc})")
+    return m2n
+
+
+def film_error_host(accum, m2n):
+    """spcbpt_film_error_host: {"pixels", "mean", "max"} of the relative standard error over the pixels with n >= 2, from (..., 4)
+    float32 arrays as read_accum / read_film_moments give them.  The per-pixel function the kernel runs; no GPU needed."""
+    lib = load_library()
+    a, m = (np.ascontiguousarray(v, dtype=np.float32) for v in (accum, m2n))
+    if a.shape != m.shape or a.shape[-1] != 4:
+        raise SpcbptError("film_error_host: accum and m2n must be (..., 4) arrays of one shape")
+    out = FilmErrorStats()
+    rc = lib.spcbpt_film_error_host(_fp(a), _fp(m), a.size // 4, C.byref(out))
+    if rc != 0:
+        raise SpcbptError(f"film_error_host failed ({rc})")
+    return out.as_dict()
+
+
 def single_leaf_tree(label=0):
     t = np.zeros(1, dtype=TREE_NODE_DTYPE)
     t[0]["leaf"] = 1
@@ -620,6 +674,15 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_denoise_params_struct_size": [],
         "spcbpt_read_denoised": [vp, vp, vp],
         "spcbpt_denoise_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
+        "spcbpt_set_film_moments": [vp, i32],
+        "spcbpt_get_film_moments": [vp, C.POINTER(i32)],
+        "spcbpt_read_film_moments": [vp, vp],
+        "spcbpt_film_moments_update_host": [f32p, f32p, u32, C.c_int64, f32p],
+        "spcbpt_film_error": [vp, C.POINTER(FilmErrorStats)],
+        "spcbpt_film_error_struct_size": [],
+        "spcbpt_film_error_host": [f32p, f32p, C.c_int64, C.POINTER(FilmErrorStats)],
+        "spcbpt_denoise_variance": [vp, C.POINTER(DenoiseParams)],
+        "spcbpt_denoise_variance_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
         "spcbpt_preprocess": [vp, i32, i32, i32],
         "spcbpt_set_pretrace": [vp, i32, i32],
         "spcbpt_train_records_count": [vp, C.POINTER(i32), C.POINTER(i32)],
@@ -682,6 +745,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
+    "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_preprocess", "spcbpt_get_subspace", "spcbpt_scene_info", "spcbpt_set_pretrace", "spcbpt_train_records_count",
     "spcbpt_train_records_read", "spcbpt_train_records_import", "spcbpt_train_records_clear", "spcbpt_preprocess_stage",
     "spcbpt_get_gamma", "spcbpt_gltf_load", "spcbpt_scene_file_load", "spcbpt_scene_file_desc", "spcbpt_scene_file_camera",
@@ -794,6 +858,28 @@ class Renderer:
         p = DenoiseParams(int(iterations), float(sigma_c), float(sigma_n), float(sigma_x))
         self._chk(self.lib.spcbpt_denoise(self.h, C.byref(p)), "denoise")
 
+    def denoise_variance(self, iterations=5, sigma_v=0.0, sigma_n=0.0, sigma_x=0.0):
+        """spcbpt_denoise_variance: the a-trous filter with its colour weight measured in the pixel's own standard error (the film's
+        moments: set_film_moments(True) before rendering; launch_features first), so that it narrows as the film converges.  A sigma
+        <= 0 takes its default.  The result is read with read_denoised(); the film is not touched."""
+        p = DenoiseParams(int(iterations), float(sigma_v), float(sigma_n), float(sigma_x))
+        self._chk(self.lib.spcbpt_denoise_variance(self.h, C.byref(p)), "denoise_variance")
+
+    def set_film_moments(self, on: bool):
+        """spcbpt_set_film_moments: keep the per-pixel second moment of the film (16 B per pixel, one small kernel per merge)."""
+        self._chk(self.lib.spcbpt_set_film_moments(self.h, 1 if on else 0), "set_film_moments")
+
+    def film_moments(self) -> bool:
+        v = C.c_int32()
+        self._chk(self.lib.spcbpt_get_film_moments(self.h, C.byref(v)), "get_film_moments")
+        return bool(v.value)
+
+    def film_error(self):
+        """spcbpt_film_error: {"pixels", "mean", "max"} of the relative standard error over the pixels with at least two samples."""
+        out = FilmErrorStats()
+        self._chk(self.lib.spcbpt_film_error(self.h, C.byref(out)), "film_error")
+        return out.as_dict()
+
     def launch_light_batch(self, first_frame, n):
         """The light passes of launch frames first_frame .. first_frame + n - 1 as one persistent launch (spcbpt_launch_light_batch)."""
         self._chk(self.lib.spcbpt_launch_light_batch(self.h, first_frame, n), "launch_light_batch")
@@ -891,6 +977,13 @@ class Renderer:
         n = np.zeros((self.height, self.width, 4), dtype=np.float32)
         self._chk(self.lib.spcbpt_read_features(self.h, a.ctypes.data, n.ctypes.data), "read_features")
         return a, n
+
+    def read_film_moments(self):
+        """(h, w, 4) float32: (M2_r, M2_g, M2_b, n) per pixel (spcbpt_read_film_moments); variance of the mean = M2 / (n (n - 1))."""
+        self.image_size()
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_film_moments(self.h, out.ctypes.data), "read_film_moments")
+        return out
 
     def read_denoised(self):
         """(rgba float32, rgba8): the result of the last denoise() and its tone-mapped frame (spcbpt_read_denoised)."""

@@ -331,6 +331,18 @@ struct Context {
     int launch_features(uint32_t subframe, int r0, int r1, int rs);
     int denoise(const spcbpt_denoise_params& p);
     void free_features();
+    // Second moment of the film (ctx_moments.hip; spcbpt_set_film_moments, off by default): one float4 per pixel (M2_r, M2_g, M2_b, n),
+    // updated by k_film_moments in front of every film merge of finish_frame.  Allocated (zeroed) at the first merge after a resize
+    // while the switch is on, freed by spcbpt_resize and by turning the switch off: a context that does not ask keeps its footprint,
+    // its launches and its film bits.
+    bool film_moments = false;
+    DevBuf<float> d_m2n;
+    DevBuf<unsigned char> d_err_scratch;   // film_error's per-block partials, then its 24-byte result
+    int set_film_moments(bool on);
+    int moments_step();                    // finish_frame: the update of this launch's pixels, queued on `rstream` in front of the merge
+    int film_error(spcbpt_film_error_stats* out);
+    int denoise_variance(const spcbpt_denoise_params& p);
+    void free_moments();
     // preprocess.hip
     Preprocessor* pre = nullptr;
     spcbpt_pretrace_path* d_pre_paths = nullptr;

@@ -139,6 +139,11 @@ int Context::sync_film() {
 int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs) {
     int rc = film_ready();
     if (rc) return rc;
+    if (film_moments) {
+        error = "launch_eye_batch: not with film moments enabled (spcbpt_set_film_moments): the batched merge takes up to 32 frames per pixel in one "
+                "pass and keeps no second moment (use spcbpt_launch per frame)";
+        return SPCBPT_ERR_STATE;
+    }
     if (!have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
     if (n < 1 || n > kMaxBatchFrames || !subframes) { error = "launch_eye_batch: 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
     if (n > (int)built_sets.size()) { error = "launch_eye_batch: fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }
@@ -205,9 +210,11 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
     return chain_end();
 }
 
-// merge this launch's `result` into accum / frame, after the previous launch's merge (the only cross-frame ordering)
+// merge this launch's `result` into accum / frame, after the previous launch's merge (the only cross-frame ordering); with film moments
+// enabled the second moment of the same pixels is updated first, from the mean the merge is about to replace (ctx_moments.hip)
 int Context::finish_frame() {
     if (int rc = chain_wait()) return rc;
+    if (film_moments) { if (int rc = moments_step()) return rc; }
     launch_film_merge(kp, rstream);
     HIP_TRY(this, hipGetLastError());
     return chain_end();

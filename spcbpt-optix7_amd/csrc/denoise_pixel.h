@@ -12,6 +12,8 @@
 
 #include <math.h>
 
+#include "moments_pixel.h"   // film_moments_sd: the variance-guided form starts from the film's moments
+
 namespace spc {
 
 static constexpr float kDenoiseAlbedoFloor = 1e-3f;   // radiance / max(albedo, floor): a black texel divides by this
@@ -85,6 +87,90 @@ SPC_DN_HD void atrous_pixel(const F& f, int x, int y, int width, int height, con
         }
     }
     for (int k = 0; k < 3; k++) out[k] = cp[k] + sum[k] / wsum;
+}
+
+// ---- the variance-guided form (spcbpt_denoise_variance): a scalar variance v of the demodulated luminance rides beside c ----------
+// what one iteration needs besides the planes: sigma_v^2, 1 / sigma_n^2, 1 / (sigma_x s)^2
+struct AtrousVarStep {
+    int step;   // s = 2^i
+    float sigma_v2, inv_sigma_n2, inv_sigma_x2;
+};
+SPC_DN_HD AtrousVarStep atrous_var_step(int i, float sigma_v, float sigma_n, float sigma_x) {
+    AtrousVarStep a;
+    a.step = 1 << i;
+    a.sigma_v2 = sigma_v * sigma_v;
+    a.inv_sigma_n2 = 1.0f / (sigma_n * sigma_n);
+    const float sx = sigma_x * (float)a.step;
+    a.inv_sigma_x2 = 1.0f / (sx * sx);
+    return a;
+}
+// v_0(p) from the film's moments m2n = (M2_r, M2_g, M2_b, n) and c0 = denoise_demodulate(accum, albedo):
+//   n >= 2:  (sum_k w_k sd_k / max(albedo_k, 1e-3))^2,  sd_k = sqrt(M2_k / (n (n - 1))),  w = (0.3, 0.6, 0.1)   (moments_pixel.h)
+//   n <  2:  L(c0)^2 -- a pixel whose variance is unknown counts as uncertain as its own value.  The one branch, on the integer n.
+SPC_DN_HD float denoise_variance_start(const float* c0, const float* albedo, const float* m2n) {
+    float s = denoise_luminance(c0);
+    if (m2n[3] >= 2.0f) {
+        float sd[3];
+        film_moments_sd(m2n, sd);
+        for (int k = 0; k < 3; k++) sd[k] = sd[k] / fmaxf(albedo[k], kDenoiseAlbedoFloor);
+        s = denoise_luminance(sd);
+    }
+    return s * s;
+}
+
+// One pixel of one iteration of the variance-guided filter.  `F` is atrous_pixel's, plus   float F::variance(int x, int y) const
+//   v~(p)   = the (1/4, 1/2, 1/4)^2 mean of v over the 3 x 3 neighbours of p at distance 1 inside the image, renormalised
+//   w(p, q) = k[a] k[b] exp(-(L(c(q)) - L(c(p)))^2 / (sigma_v^2 v~(p) + (1e-3 (1e-2 + L(c(p))))^2) - |n(q) - n(p)|^2 / sigma_n^2
+//                           - |X(q) - X(p)|^2 / (sigma_x s)^2)
+//   out.rgb = c(p) + sum w (c(q) - c(p)) / sum w,    out.w = sum w^2 v(q) / (sum w)^2     (the variance of that weighted mean)
+// The colour term is measured in the pixel's own standard deviation, so the filter narrows as the film converges: with v = 0 only
+// neighbours within a thousandth of the pixel's luminance still count.  Smooth weights only; the centre tap (w = 9 / 64) keeps the
+// sum non-empty; a constant image comes back bit for bit.
+template <class F>
+SPC_DN_HD void atrous_var_pixel(const F& f, int x, int y, int width, int height, const AtrousVarStep& a, float* out) {
+    const float kern[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float pre[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+    float cp[3], np[3], Xp[3];
+    f.fetch(x, y, cp, np, Xp);
+    float vs = 0.0f, gs = 0.0f;
+    for (int b = -1; b <= 1; b++) {
+        const int qy = y + b;
+        if (qy < 0 || qy >= height) continue;
+        for (int t = -1; t <= 1; t++) {
+            const int qx = x + t;
+            if (qx < 0 || qx >= width) continue;
+            const float g = pre[t + 1] * pre[b + 1];
+            vs += g * f.variance(qx, qy);
+            gs += g;
+        }
+    }
+    const float Lp = denoise_luminance(cp);
+    const float floor_l = 1e-3f * (1e-2f + Lp);
+    const float inv_den = 1.0f / (a.sigma_v2 * (vs / gs) + floor_l * floor_l);
+    float sum[3] = {0.0f, 0.0f, 0.0f}, wsum = 0.0f, vsum = 0.0f;
+    for (int b = -2; b <= 2; b++) {
+        const int qy = y + a.step * b;
+        if (qy < 0 || qy >= height) continue;
+        for (int t = -2; t <= 2; t++) {
+            const int qx = x + a.step * t;
+            if (qx < 0 || qx >= width) continue;
+            float cq[3], nq[3], Xq[3];
+            f.fetch(qx, qy, cq, nq, Xq);
+            float dc[3], dn2 = 0.0f, dx2 = 0.0f;
+            for (int k = 0; k < 3; k++) {
+                dc[k] = cq[k] - cp[k];
+                const float dn = nq[k] - np[k], dX = Xq[k] - Xp[k];
+                dn2 += dn * dn; dx2 += dX * dX;
+            }
+            const float dL = denoise_luminance(cq) - Lp;
+            const float w = kern[t + 2] * kern[b + 2] * expf(-(dL * dL * inv_den) - dn2 * a.inv_sigma_n2 - dx2 * a.inv_sigma_x2);
+            for (int k = 0; k < 3; k++) sum[k] += w * dc[k];
+            wsum += w;
+            vsum += w * w * f.variance(qx, qy);
+        }
+    }
+    for (int k = 0; k < 3; k++) out[k] = cp[k] + sum[k] / wsum;
+    out[3] = vsum / (wsum * wsum);
 }
 
 }  // namespace spc

@@ -23,5 +23,8 @@ struct DenoiseParams {  // passed by value as the kernel argument block of k_dem
 void launch_demodulate(const DenoiseParams& p, hipStream_t s);                                        // accum, features -> ping, position
 void launch_atrous(const DenoiseParams& p, const AtrousStep& a, bool ping_to_pong, hipStream_t s);    // one iteration
 void launch_remodulate(const DenoiseParams& p, bool from_pong, hipStream_t s);                        // c_last -> denoised, frame
+// the variance-guided form (spcbpt_denoise_variance): the variance rides in the .w of ping / pong; launch_remodulate ends it too
+void launch_demodulate_var(const DenoiseParams& p, const float* m2n, hipStream_t s);                      // accum, features, moments -> ping, position
+void launch_atrous_var(const DenoiseParams& p, const AtrousVarStep& a, bool ping_to_pong, hipStream_t s); // one iteration
 
 }  // namespace spc

@@ -1,7 +1,9 @@
 """The grid behind the denoiser's default parameters (include/spcbpt.h): RMSE of the denoised 4-frame "pt" image of the
 Cornell box at 64 x 64 against a disjoint 512-frame mean, for sigma_c in {1, 2, 4} x sigma_n in {0.25, 0.5, 1} x sigma_x in
 {0.01, 0.03, 0.1} of the bounding-box diagonal, and the denoised / noisy ratios of the defaults on the Cornell box and the textured
-bedroom.  Needs a GPU.   python tools/denoise_grid.py"""
+bedroom.  Then the grid behind SPCBPT_DENOISE_SIGMA_V: the variance-guided filter (spcbpt_denoise_variance) for sigma_v in
+{2, 4, 8} on the same box at 4 and at 64 frames against a 512-frame mean disjoint from both; the default is the value with the lowest
+sum of the two RMSEs.  Needs a GPU.   python tools/denoise_grid.py"""
 import os
 import sys
 
@@ -44,6 +46,34 @@ def rmse(a, b):
     return float(np.sqrt(np.mean((a - b) ** 2)))
 
 
+def variance_grid(scene, w=64, h=64, counts=(4, 64), sigmas=(2.0, 4.0, 8.0)):
+    r = setup(scene, w, h)
+    r.set_film_moments(True)
+    shots = {}
+    for f in range(max(counts)):
+        r.launch("pt", f)
+        r.launch_features(f)
+        if f + 1 in counts:
+            s = {"film": r.read_accum()[..., :3].astype(np.float64), "error": r.film_error()["mean"]}
+            for sv in sigmas:
+                r.denoise_variance(5, sv)
+                s[sv] = r.read_denoised()[0][..., :3].astype(np.float64)
+            r.denoise(5)
+            s["plain"] = r.read_denoised()[0][..., :3].astype(np.float64)
+            shots[f + 1] = s
+    n0 = max(counts)
+    for f in range(n0, n0 + REF):
+        r.launch("pt", f)
+    ref = ((n0 + REF) * r.read_accum()[..., :3].astype(np.float64) - n0 * shots[n0]["film"]) / REF
+    print(f"variance-guided filter, cornell {w}x{h}, RMSE against a disjoint {REF}-frame mean:")
+    for n in counts:
+        s = shots[n]
+        print(f"  {n} frames (film error {s['error']:.4f}): film {rmse(s['film'], ref):.5f}, plain a-trous {rmse(s['plain'], ref):.5f}, "
+              + ", ".join(f"sigma_v {sv:g}: {rmse(s[sv], ref):.5f}" for sv in sigmas))
+    for sv in sorted(sigmas, key=lambda sv: sum(rmse(shots[n][sv], ref) for n in counts)):
+        print(f"  sigma_v {sv:g}: sum over {counts} frames {sum(rmse(shots[n][sv], ref) for n in counts):.5f}")
+
+
 def main():
     scene = pkg.scenes.cornell_box()
     v = np.asarray(scene.vertices, np.float64)
@@ -69,6 +99,7 @@ def main():
     den = r.read_denoised()[0][..., :3].astype(np.float64)
     ref = reference(r, a4)
     print(f"bedroom 64x64: RMSE {rmse(a4, ref):.5f} -> {rmse(den, ref):.5f} (ratio {rmse(den, ref) / rmse(a4, ref):.3f})")
+    variance_grid(scene)
 
 
 if __name__ == "__main__":

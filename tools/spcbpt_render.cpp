@@ -8,7 +8,10 @@
 // --denoise: a first-hit feature launch beside every frame and one a-trous denoise (spcbpt_denoise, default parameters) after the last;
 // writes <out>_denoised.pfm / .ppm next to the usual files.  --features: writes the feature buffers as <out>_albedo.pfm,
 // <out>_normal.pfm and <out>_depth.pfm (depth in all three channels).
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--features] [--out prefix]
+// --denoise-variance: the same with the variance-guided filter (spcbpt_denoise_variance; switches the film's moments on).
+// --target-error E [--check-every K]: switches the film's moments on and renders until spcbpt_film_error's mean is <= E (asked every K
+// frames, default 8, from the second frame on) or --frames is reached; prints the frames used and the error reached.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -48,13 +51,15 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--features] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
     int env_mode = 0;
-    bool minimal = false, emissive = false, denoise = false, features = false;
+    bool minimal = false, emissive = false, denoise = false, features = false, denoise_variance = false;
+    double target_error = 0.0;   // > 0: stop once the film's mean relative standard error is there
+    int check_every = 8;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -65,7 +70,10 @@ int main(int argc, char** argv) {
         else if (a == "--env-mode" && i + 1 < argc) env_mode = atoi(argv[++i]);
         else if (a == "--emissive") emissive = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-variance") denoise = denoise_variance = true;
         else if (a == "--features") features = true;
+        else if (a == "--target-error" && i + 1 < argc) target_error = atof(argv[++i]);
+        else if (a == "--check-every" && i + 1 < argc) check_every = atoi(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -110,6 +118,9 @@ int main(int argc, char** argv) {
     CHECK(ctx, spcbpt_set_environment_mode(ctx, env_mode));
     CHECK(ctx, spcbpt_set_camera_lookat(ctx, eye, lookat, up, fov, (float)width / (float)height));
     CHECK(ctx, spcbpt_resize(ctx, width, height));
+    const bool moments = denoise_variance || target_error > 0.0;
+    if (moments) CHECK(ctx, spcbpt_set_film_moments(ctx, 1));
+    if (check_every < 1) check_every = 1;
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 0, 1};
     CHECK(ctx, spcbpt_set_light_trace(ctx, &lt));
     auto t0 = std::chrono::steady_clock::now();
@@ -121,6 +132,7 @@ int main(int argc, char** argv) {
     }
     auto t1 = std::chrono::steady_clock::now();
     printf("preprocessing: %.2f s\n", std::chrono::duration<double>(t1 - t0).count());
+    spcbpt_film_error_stats reached = {0, 0.0, 0.0};
     unsigned lt_frame = 1000000;  // continues after the Q passes of the preprocessing like lt_params.launch_frame
     for (int f = 0; f < frames; f++) {
         if (alg == "SPCBPT_eye" || lt_alg) {  // launchLVCTrace (optixPathTracer.cpp:515-522)
@@ -129,10 +141,20 @@ int main(int argc, char** argv) {
         }
         CHECK(ctx, spcbpt_launch(ctx, alg.c_str(), (uint32_t)f, 0, height, 1));  // launchSubframe (609-635)
         if (denoise || features) CHECK(ctx, spcbpt_launch_features(ctx, (uint32_t)f, 0, height, 1));   // the same subframe's primary rays
+        if (target_error > 0.0 && f >= 1 && ((f + 1) % check_every == 0 || f + 1 == frames)) {
+            CHECK(ctx, spcbpt_film_error(ctx, &reached));
+            if (reached.pixels > 0 && reached.mean <= target_error) { frames = f + 1; break; }
+        }
+    }
+    if (target_error > 0.0) {
+        if (frames < 2) CHECK(ctx, spcbpt_film_error(ctx, &reached));
+        printf("target error %g: %d frames used, error reached %.6g (max %.6g over %lld pixels)\n", target_error, frames, reached.mean, reached.max,
+               (long long)reached.pixels);
     }
     if (denoise) {
         const spcbpt_denoise_params dp = {5, 0.0f, 0.0f, 0.0f};   // the defaults of include/spcbpt.h
-        CHECK(ctx, spcbpt_denoise(ctx, &dp));
+        if (denoise_variance) CHECK(ctx, spcbpt_denoise_variance(ctx, &dp));
+        else CHECK(ctx, spcbpt_denoise(ctx, &dp));
     }
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
