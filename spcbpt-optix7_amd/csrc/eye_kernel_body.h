@@ -45,7 +45,7 @@
     bool alive = false, exhausted = false;
     uint32_t pool_tile = 0;
     int pool_left = 0;
-    uint32_t x = 0, y = 0;
+    uint32_t xy = 0;   // the pixel of the lane's path, x | y << 16: one register across the pass (the packing of `pend_xy`)
     WalkState w;
     EyeVertex cur;
     f3 result = mk3(0.0f);
@@ -60,6 +60,14 @@
     // iteration later.  Its lane does not wait for them: it parks the pixel and the radiance so far (`pend_*`), starts the next
     // pixel-sample at once (`fresh`: the camera vertex is installed after the connect phase, which still reads `cur`), and
     // writes the parked pixel when the connections have been added.
+    // Where the parked radiance waits: the kernel spills, and what is alive across the traversal pass is what it spills.  A single-frame
+    // launch accumulates through film_write and keeps `pend_result` in registers.  A BATCH launch stores each frame's samples with a plain
+    // store to that frame's own film, which nothing else touches before k_film_merge_batch (a pixel-sample of a frame belongs to one lane;
+    // the batched form refuses while film moments are on): there the lane stores `result` when it parks, and only an owner one of whose
+    // owed connections came back unoccluded reads the value again after the connect phase, adds its contributions in connection order and
+    // stores the sum.  The value returns from memory bit for bit, so the chain of FP32 additions is the single-frame form's.
+    // (Measured, profiles/r08_experiments.md: 144 -> 128 B of scratch per lane in the batched plain form, 160 -> 128 B in the general one;
+    // the read issued BEFORE the job loop, to cover its latency, keeps six more registers alive through connect_vertices and spills more.)
     bool pend_valid = false, fresh = false;
     uint32_t pend_xy = 0;
     f3 pend_result = mk3(0.0f);
@@ -88,13 +96,17 @@
                 const uint32_t slot = (uint32_t)(64 - pool_left + my_rank);
                 uint32_t nx, ny;
                 if (tile_pixel(p, pool_tile, slot, nx, ny)) {
-                    if (alive) { pend_valid = true; pend_xy = x | (y << 16); pend_result = result; pend_fid = fid; }
-                    x = nx; y = ny;
+                    if (alive) {
+                        pend_valid = true; pend_xy = xy; pend_fid = fid;
+                        if (BATCH) film_store(p.frames[fid].result, p.width, xy & 0xffffu, xy >> 16, result);   // parked in the frame's film
+                        else pend_result = result;
+                    }
+                    xy = nx | (ny << 16);
                     fid = pool_fid;
                     alive = true;
                     has_ray = true;
                     fresh = true;
-                    w.dir = camera_ray(p, x, y, w.seed, BATCH ? p.frames[fid].subframe : p.subframe);
+                    w.dir = camera_ray(p, nx, ny, w.seed, BATCH ? p.frames[fid].subframe : p.subframe);
                     w.origin = ld3(p.eye);
                     w.done = false;
                     w.next_flux = mk3(0.0f);
@@ -210,7 +222,17 @@
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                f3 sum = pend_valid ? pend_result : result;
+                // BATCH: a parked pixel that is owed a connection comes back from its frame's film
+                float4* pend_px = nullptr;
+                f3 sum = result;
+                if (pend_valid) {
+                    if (!BATCH) sum = pend_result;
+                    else if (my_live) {
+                        pend_px = reinterpret_cast<float4*>(p.frames[pend_fid].result) + ((size_t)(pend_xy >> 16) * p.width + (pend_xy & 0xffffu));
+                        const float4 parked = *pend_px;
+                        sum = mk3(parked.x, parked.y, parked.z);
+                    }
+                }
 #pragma unroll
                 for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                     if (my_live & (1u << it)) {
@@ -218,13 +240,13 @@
                         if (r.w != 0.0f) sum += mk3(r.x, r.y, r.z);
                     }
                 }
-                if (pend_valid) pend_result = sum;
-                else result = sum;
+                if (!pend_valid) result = sum;
+                else if (!BATCH) pend_result = sum;
+                else if (my_live) *pend_px = make_float4(sum.x, sum.y, sum.z, 1.0f);   // (film_store's record)
             }
         }
         if (pend_valid) {
-            if (BATCH) film_store(p.frames[pend_fid].result, p.width, pend_xy & 0xffffu, pend_xy >> 16, pend_result);
-            else film_write(p, pend_xy & 0xffffu, pend_xy >> 16, pend_result);
+            if (!BATCH) film_write(p, pend_xy & 0xffffu, pend_xy >> 16, pend_result);   // (BATCH: the pixel already stands in its frame's film)
             pend_valid = false;
         }
         if (fresh) {  // init_EyeSubpath (raygen.cu:216-231)
@@ -331,8 +353,8 @@
             for (int it = 0; it < SPCBPT_CONNECTION_N; it++) w_ray[it * 64 + lane] = make_float4(0.f, 0.f, 0.f, -1.0f);
         }
         if (alive && finished) {
-            if (BATCH) film_store(p.frames[fid].result, p.width, x, y, result);
-            else film_write(p, x, y, result);
+            if (BATCH) film_store(p.frames[fid].result, p.width, xy & 0xffffu, xy >> 16, result);
+            else film_write(p, xy & 0xffffu, xy >> 16, result);
             alive = false;
         }
         SPC_PHASE(C_T_SHADE);
