@@ -544,6 +544,73 @@ int spcbpt_denoise_variance_host(const float* accum_rgba, const float* m2n, cons
                                  const float eye[3], const float U[3], const float V[3], const float W[3],
                                  int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
 
+/* History reprojection (no reference counterpart), opt-in: the converged image of one camera carried into the next through the
+ * first-hit depth, so that a camera move does not fall back to one sample per pixel.  The scene is static, so where a pixel was is
+ * a function of its depth and of the two cameras; nothing else is kept.  A context that never calls these keeps its footprint, its
+ * launches and its film bits; film, frame, features, moments and counters are never written.
+ * A HISTORY is taken at capture time: a float4 plane H(q) = (rgb, n), the image and its effective frame count; a float4 plane G(q),
+ * the normal / depth feature plane as it stood; the camera (eye_h, U_h, V_h, W_h); the film size.  A PRIOR is one float4 plane
+ * R(p) = (rgb, m) in the current view, m the number of frames the prior is worth at p.
+ * Reproject, for every pixel p = (x, y) of the current film, float32 without contraction, with nd = normal_depth(p):
+ *   nd.w <= 0 (a miss):  R(p) = 0
+ *   P = eye + X(p),  X(p) = d_c(p) nd.w as in the denoiser (the centre ray);   c = P - eye_h,   D = U_h . (V_h x W_h)
+ *   g = c . (U_h x V_h) / D,   dx = (c . (V_h x W_h) / D) / g,   dy = (c . (W_h x U_h) / D) / g      (the algebra of camera_splat)
+ *   g <= 0:  R(p) = 0
+ *   fx = clamp((dx + 1) / 2 width - 0.5, -2, width + 1),  x0 = floor(fx),  ax = fx - x0;   fy, y0, ay likewise with height
+ *   the four taps q = (x0 + i, y0 + j), i, j in {0, 1}; a tap outside the image or with G(q).w <= 0 has weight 0, else
+ *   b_q = (i ? ax : 1 - ax) (j ? ay : 1 - ay),    X_q = eye_h + d_c,h(q) G(q).w
+ *   w_q = b_q exp(-(nd.xyz . (X_q - P))^2 / sigma_x^2 - |G(q).xyz - nd.xyz|^2 / sigma_n^2)
+ *   S = sum w_q,   C = sum w_q H(q).rgb,   N = sum w_q H(q).n
+ *   S < 1e-6:  R(p) = 0,   else R(p) = (C / S, S min(N / S, max_history))
+ * The weights are smooth and the floor is harmless (the bilinear weight of a tap is zero where it enters or leaves); the only
+ * decisions on computed values are g <= 0, where every tap is outside anyway, and the S cut, a jump of at most 1e-6 frames -- so a
+ * float64 evaluation agrees everywhere.  A disoccluded pixel finds taps on another surface: the plane distance and the normal
+ * difference take its weight, m, to zero and the film alone shows there.
+ * Resolve(frames), frames >= 1, Nf = (float)frames, m = R(p).w (0 where no prior is live):
+ *   out(p).rgb = (m R(p).rgb + Nf accum(p).rgb) / (m + Nf),   out(p).w = m + Nf;   an RGBA8 plane holds the film's tone map of out.rgb
+ * (while no prior is live out.rgb is accum.rgb bit for bit -- the value of the formula with m = 0, without its two roundings)
+ * Capture(frames), frames >= 1: H becomes the resolve of the current film (a live prior is folded in, so a chain of moves keeps its
+ * history), G a copy of the current normal_depth plane, the current camera is stored, and the prior stops being live.
+ * A parameter <= 0 selects its default -- for sigma_x (a length in scene units) SPCBPT_REPROJECT_SIGMA_X_FRACTION of the diagonal of
+ * the scene's bounding box, as in spcbpt_denoise; a NaN is SPCBPT_ERR_INVALID_ARG.  The defaults (0.5, 0.002, 32) are the triple with
+ * the lowest summed rank on the grid {0.1, 0.25, 0.5} x {0.002, 0.005, 0.02} x {16, 32, 64}: RMSE of resolve(1) and resolve(8) against
+ * a converged image after orbits of 2 and 8 degrees, Cornell box and bedroom (tools/reproject_grid.py). */
+typedef struct spcbpt_reproject_params {
+    float sigma_n, sigma_x, max_history;
+} spcbpt_reproject_params;
+#define SPCBPT_REPROJECT_SIGMA_N 0.5f
+#define SPCBPT_REPROJECT_SIGMA_X_FRACTION 0.002f
+#define SPCBPT_REPROJECT_MAX_HISTORY 32.0f
+int spcbpt_reproject_params_struct_size(void);   /* sizeof(spcbpt_reproject_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+/* The three passes are links of the film-merge chain like spcbpt_denoise: they see every merge queued before them, are asynchronous,
+ * and their kernel-time spans are "history_capture", "reproject" and "resolve".  All need a film and no deferred frame outstanding;
+ * capture and reproject need a feature launch since the last spcbpt_resize, reproject a captured history of the current film size
+ * (else SPCBPT_ERR_STATE, with text); frames == 0 is SPCBPT_ERR_INVALID_ARG.  Resolve works without a prior and is then the film
+ * itself.  Five planes, 68 B per pixel (H, G, the prior, the resolved image and its RGBA8 frame), are allocated at the first
+ * capture; spcbpt_resize and spcbpt_history_reset free them, spcbpt_clear_accum leaves the history alone.
+ * The intended sequence: capture at the old camera, spcbpt_set_camera, spcbpt_launch(alg, 0), spcbpt_launch_features(0), reproject,
+ * then resolve(1), spcbpt_launch(alg, 1), resolve(2), ...  The features of both views should be those of subframe 0 (centre rays:
+ * P is then the first hit exactly); later feature means still work, they only blur P by the jitter.
+ * Not covered: sky pixels (a miss has no depth), the moments plane and spcbpt_film_error (they keep describing the film), sharded
+ * films, the batched and deferred launch forms, moving geometry.  A reprojected highlight lags for up to max_history frames. */
+int spcbpt_history_capture(spcbpt_ctx* ctx, uint32_t frames);
+int spcbpt_history_reproject(spcbpt_ctx* ctx, const spcbpt_reproject_params* params);
+int spcbpt_history_resolve(spcbpt_ctx* ctx, uint32_t frames);
+/* Drops history and prior and frees their planes (waits for the context's streams). */
+int spcbpt_history_reset(spcbpt_ctx* ctx);
+/* Waits like spcbpt_read_denoised and copies the float4 resolved image, its RGBA8 frame, the prior and H (any pointer may be NULL).
+ * SPCBPT_ERR_STATE for a plane that does not exist yet: nothing resolved, no live prior, nothing captured. */
+int spcbpt_read_history(spcbpt_ctx* ctx, float* resolved_rgba, uint8_t* resolved_rgba8, float* prior_rgba, float* history_rgbn);
+/* The same per-pixel functions on caller buffers on the host; no context and no GPU needed.  Cameras as spcbpt_set_camera takes
+ * them, float4-per-pixel planes as the read-backs give them.  Without a scene the default of sigma_x is
+ * SPCBPT_REPROJECT_SIGMA_X_FRACTION of sigma_x_default_diag (<= 0: 1).  The inputs are not written.  SPCBPT_ERR_INVALID_ARG for a
+ * NULL pointer (the resolve's prior may be NULL: no prior), an empty image, a NaN parameter or frames == 0. */
+int spcbpt_history_reproject_host(const float eye[3], const float U[3], const float V[3], const float W[3], const float* normal_depth_rgba,
+                                  const float eye_h[3], const float U_h[3], const float V_h[3], const float W_h[3],
+                                  const float* history_normal_depth_rgba, const float* history_rgbn, int width, int height,
+                                  const spcbpt_reproject_params* params, float sigma_x_default_diag, float* prior_out);
+int spcbpt_history_resolve_host(const float* prior_rgba, const float* accum_rgba, uint32_t frames, int64_t n_pixels, float* out_rgba);
+
 int spcbpt_get_counters(spcbpt_ctx* ctx, spcbpt_counters* out);
 int spcbpt_reset_counters(spcbpt_ctx* ctx);
 /* Developer aid (no reference counterpart): wave-clock totals the counting build of the "SPCBPT_eye" megakernel spent in
@@ -876,6 +943,18 @@ int spcbpt_viewer_set_fps(spcbpt_viewer* v, float fps);
  * spcbpt_viewer_set_light_ahead(v, on) = set_pipeline(v, on ? 1 : 0). */
 int spcbpt_viewer_set_pipeline(spcbpt_viewer* v, int mode);
 int spcbpt_viewer_set_light_ahead(spcbpt_viewer* v, int on);
+/* History reprojection in the loop (spcbpt_history_*; off by default, and then nothing of it is called).  While on:
+ *   - every subframe-0 frame is followed by spcbpt_launch_features(ctx, 0, ...), the centre rays' first hits;
+ *   - a frame that saw a camera change and nothing else -- no resize, no algorithm switch, no P restart -- with at least one frame
+ *     shown under the old camera drops the frame traced ahead as always, calls spcbpt_history_capture(ctx, frames shown so far)
+ *     before spcbpt_set_camera, and queues spcbpt_history_reproject with the defaults behind the features of the new view;
+ *   - every shown frame is followed by spcbpt_history_resolve(ctx, subframe_index + 1), behind that frame's merge and, in mode 2, in
+ *     front of spcbpt_launch_deferred.  What to display is then spcbpt_read_history's resolved image; the film is what it always was.
+ * Any other restart (resize, algorithm switch, P) and flipping the switch call spcbpt_history_reset; flipping the switch also
+ * restarts the accumulation.  The three pipeline modes show the same resolved frames.  With a null context the switch is state
+ * only.  `live` tells whether a prior is live on the context, i.e. whether the resolved image differs from the film. */
+int spcbpt_viewer_set_reproject(spcbpt_viewer* v, int on);
+int spcbpt_viewer_get_reproject(spcbpt_viewer* v, int* on, int* live);
 int spcbpt_viewer_frame(spcbpt_viewer* v);
 int spcbpt_viewer_get_state(spcbpt_viewer* v, spcbpt_viewer_state* state);
 const char* spcbpt_viewer_alg_name(int alg_id);

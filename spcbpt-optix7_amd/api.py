@@ -53,6 +53,10 @@ class DenoiseParams(C.Structure):   # spcbpt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_x", C.c_float)]
 
 
+class ReprojectParams(C.Structure):   # spcbpt_reproject_params
+    _fields_ = [("sigma_n", C.c_float), ("sigma_x", C.c_float), ("max_history", C.c_float)]
+
+
 class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
     _fields_ = [("pixels", C.c_int64), ("mean", C.c_double), ("max", C.c_double)]
 
@@ -376,6 +380,45 @@ def denoise_variance_host(accum, m2n, albedo, normal_depth, eye, U, V, W, iterat
     return out
 
 
+def history_reproject_host(camera, normal_depth, history_camera, history_normal_depth, history_rgbn, sigma_n=0.0, sigma_x=0.0, max_history=0.0, diag=0.0):
+    """spcbpt_history_reproject_host: the prior of Renderer.history_reproject on (h, w, 4) float32 arrays -- the current view's
+    normal / depth plane, the history's, and the history image (rgb, n) -- with the two cameras as (eye, U, V, W).  Host code in float32
+    -- the per-pixel function the kernel runs; no GPU needed.  A parameter <= 0 takes its default (sigma_x: a fraction of `diag`).
+    Returns the (h, w, 4) prior (rgb, m); the inputs are not written."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (normal_depth, history_normal_depth, history_rgbn)]
+    h, w = a[0].shape[:2]
+    if any(v.shape != (h, w, 4) for v in a):
+        raise SpcbptError("history_reproject_host: the three planes must be (h, w, 4) arrays of one size")
+    cam = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in tuple(camera) + tuple(history_camera)]
+    if len(cam) != 8:
+        raise SpcbptError("history_reproject_host: a camera is (eye, U, V, W)")
+    out = np.zeros((h, w, 4), dtype=np.float32)
+    p = ReprojectParams(float(sigma_n), float(sigma_x), float(max_history))
+    rc = lib.spcbpt_history_reproject_host(*[_fp(v) for v in cam[:4]], _fp(a[0]), *[_fp(v) for v in cam[4:]], _fp(a[1]), _fp(a[2]), w, h,
+                                           C.byref(p), C.c_float(diag), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"history_reproject_host failed ({rc})")
+    return out
+
+
+def history_resolve_host(prior, accum, frames):
+    """spcbpt_history_resolve_host: the blend of Renderer.history_resolve on (..., 4) float32 arrays -- the prior (or None: no prior)
+    and the film's mean of `frames` frames.  The per-pixel function the kernel runs; no GPU needed.  Returns (rgb, m + frames)."""
+    lib = load_library()
+    a = np.ascontiguousarray(accum, dtype=np.float32)
+    r = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
+    if a.shape[-1] != 4 or (r is not None and r.shape != a.shape):
+        raise SpcbptError("history_resolve_host: prior and accum must be (..., 4) arrays of one shape")
+    if int(frames) < 0 or int(frames) >= 2**32:
+        raise SpcbptError("history_resolve_host: frames out of range")
+    out = np.zeros(a.shape, dtype=np.float32)
+    rc = lib.spcbpt_history_resolve_host(_fp(r) if r is not None else None, _fp(a), int(frames), a.size // 4, _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"history_resolve_host failed ({rc})")
+    return out
+
+
 def film_moments_update_host(mean_before, sample, subframe, m2n):
     """spcbpt_film_moments_update_host: one merge's update of the moment plane `m2n` ((..., 4) float32, C-contiguous, updated IN PLACE)
     from the film before the merge and the frame's samples (same shape).  The per-pixel function the kernel runs; no GPU needed."""
@@ -484,6 +527,16 @@ class Viewer:
 
     def set_light_ahead(self, on):
         self._chk(self.lib.spcbpt_viewer_set_light_ahead(self.h, int(on)), "viewer_set_light_ahead")
+
+    def set_reproject(self, on):
+        """spcbpt_viewer_set_reproject: carry the shown image across camera moves (off by default); flipping it restarts the accumulation."""
+        self._chk(self.lib.spcbpt_viewer_set_reproject(self.h, int(bool(on))), "viewer_set_reproject")
+
+    def get_reproject(self):
+        """{"on", "live"}: the switch, and whether a prior is live (the resolved image differs from the film)."""
+        on, live = C.c_int32(), C.c_int32()
+        self._chk(self.lib.spcbpt_viewer_get_reproject(self.h, C.byref(on), C.byref(live)), "viewer_get_reproject")
+        return {"on": int(on.value), "live": int(live.value)}
 
     def set_pipeline(self, mode: int):
         """0 the reference's order, 1 next light pass beside the eye kernel, 2 (default) next frame traced while this one is shown."""
@@ -682,6 +735,11 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_film_error_struct_size": [],
         "spcbpt_film_error_host": [f32p, f32p, C.c_int64, C.POINTER(FilmErrorStats)],
         "spcbpt_denoise_variance": [vp, C.POINTER(DenoiseParams)],
+        "spcbpt_history_capture": [vp, C.c_uint32], "spcbpt_history_reproject": [vp, C.POINTER(ReprojectParams)], "spcbpt_history_resolve": [vp, C.c_uint32],
+        "spcbpt_history_reset": [vp], "spcbpt_reproject_params_struct_size": [], "spcbpt_read_history": [vp, vp, vp, vp, vp],
+        "spcbpt_history_reproject_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(ReprojectParams), C.c_float, f32p],
+        "spcbpt_history_resolve_host": [f32p, f32p, C.c_uint32, C.c_int64, f32p],
+        "spcbpt_viewer_set_reproject": [vp, i32], "spcbpt_viewer_get_reproject": [vp, C.POINTER(i32), C.POINTER(i32)],
         "spcbpt_denoise_variance_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
         "spcbpt_preprocess": [vp, i32, i32, i32],
         "spcbpt_set_pretrace": [vp, i32, i32],
@@ -746,6 +804,8 @@ EXPORTED_SYMBOLS = [
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
+    "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
+    "spcbpt_history_reproject_host", "spcbpt_history_resolve_host", "spcbpt_viewer_set_reproject", "spcbpt_viewer_get_reproject",
     "spcbpt_preprocess", "spcbpt_get_subspace", "spcbpt_scene_info", "spcbpt_set_pretrace", "spcbpt_train_records_count",
     "spcbpt_train_records_read", "spcbpt_train_records_import", "spcbpt_train_records_clear", "spcbpt_preprocess_stage",
     "spcbpt_get_gamma", "spcbpt_gltf_load", "spcbpt_scene_file_load", "spcbpt_scene_file_desc", "spcbpt_scene_file_camera",
@@ -983,6 +1043,33 @@ class Renderer:
         self.image_size()
         out = np.zeros((self.height, self.width, 4), dtype=np.float32)
         self._chk(self.lib.spcbpt_read_film_moments(self.h, out.ctypes.data), "read_film_moments")
+        return out
+
+    def history_capture(self, frames):
+        """spcbpt_history_capture: keep what history_resolve(frames) would show, with the feature plane and the camera, as the
+        history of the next reprojection.  Needs launch_features since the last resize."""
+        self._chk(self.lib.spcbpt_history_capture(self.h, int(frames)), "history_capture")
+
+    def history_reproject(self, sigma_n=0.0, sigma_x=0.0, max_history=0.0):
+        """spcbpt_history_reproject: the captured history carried into the current view through the first-hit depth (the prior).
+        Needs launch_features(0) of the current view; a parameter <= 0 takes its default."""
+        p = ReprojectParams(float(sigma_n), float(sigma_x), float(max_history))
+        self._chk(self.lib.spcbpt_history_reproject(self.h, C.byref(p)), "history_reproject")
+
+    def history_resolve(self, frames):
+        """spcbpt_history_resolve: the prior (if one is live) blended with the film's mean of `frames` frames; read with read_history()."""
+        self._chk(self.lib.spcbpt_history_resolve(self.h, int(frames)), "history_resolve")
+
+    def history_reset(self):
+        self._chk(self.lib.spcbpt_history_reset(self.h), "history_reset")
+
+    def read_history(self, resolved=True, frame=True, prior=False, history=False):
+        """spcbpt_read_history: a dict of the planes asked for -- "resolved" (h, w, 4) float32 and its tone-mapped "frame" (h, w, 4) uint8,
+        the "prior" (rgb, m), the captured "history" (rgb, n).  SpcbptError (-5) for a plane that does not exist yet."""
+        self.image_size()
+        want = {"resolved": (resolved, np.float32), "frame": (frame, np.uint8), "prior": (prior, np.float32), "history": (history, np.float32)}
+        out = {k: np.zeros((self.height, self.width, 4), dtype=t) for k, (on, t) in want.items() if on}
+        self._chk(self.lib.spcbpt_read_history(self.h, *[out[k].ctypes.data if k in out else None for k in want]), "read_history")
         return out
 
     def read_denoised(self):

@@ -2,7 +2,12 @@
 // One __host__ __device__ function, shared by k_lt_splat (dev_splat.h) and the exported spcbpt_camera_splat (ctx_splat.hip), so that
 // the projection is testable without a GPU.  Float32 throughout, no contraction (the library's flags), the same operations on both sides.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define SPC_CS_HD __host__ __device__ inline
+#else
+#define SPC_CS_HD inline   // plain g++ (reproject_host.cpp): the same functions without the HIP headers
+#endif
 
 #include <math.h>
 
@@ -15,18 +20,33 @@ namespace spc {
 //   px = floor((dx + 1) / 2 w)            py = floor((dy + 1) / 2 h)           (row 0 at dy = -1)
 //   weight = w h |c / g|^3 / (4 |D|)      the reciprocal solid angle of a pixel seen along c: the pixel's parallelogram on the plane
 //                                         g = 1 has area (2 / w)(2 / h) |U x V|, lies |c / g| away and is tilted by D / (|U x V| |c / g|)
-// Returns false (and writes nothing) when the point does not land inside the image.
-__host__ __device__ inline bool camera_splat(const float* eye, const float* U, const float* V, const float* W, int width, int height,
-                                             const float* point, float& dx, float& dy, int& px, int& py, float& weight) {
-    const float c[3] = {point[0] - eye[0], point[1] - eye[1], point[2] - eye[2]};
+// camera_project is that algebra alone -- c, D, g, dx, dy, whatever g is (dx and dy mean nothing unless g > 0) -- shared by camera_splat
+// below and by the history reprojection (reproject_pixel.h), which lands a first hit in an EARLIER camera.
+struct CameraProjection {
+    float c[3], D, g, dx, dy;
+};
+SPC_CS_HD CameraProjection camera_project(const float* eye, const float* U, const float* V, const float* W, const float* point) {
+    CameraProjection r;
+    r.c[0] = point[0] - eye[0]; r.c[1] = point[1] - eye[1]; r.c[2] = point[2] - eye[2];
+    const float* c = r.c;
     const float vw[3] = {V[1] * W[2] - V[2] * W[1], V[2] * W[0] - V[0] * W[2], V[0] * W[1] - V[1] * W[0]};
     const float wu[3] = {W[1] * U[2] - W[2] * U[1], W[2] * U[0] - W[0] * U[2], W[0] * U[1] - W[1] * U[0]};
     const float uv[3] = {U[1] * V[2] - U[2] * V[1], U[2] * V[0] - U[0] * V[2], U[0] * V[1] - U[1] * V[0]};
-    const float D = U[0] * vw[0] + U[1] * vw[1] + U[2] * vw[2];
-    const float g = (c[0] * uv[0] + c[1] * uv[1] + c[2] * uv[2]) / D;
+    r.D = U[0] * vw[0] + U[1] * vw[1] + U[2] * vw[2];
+    r.g = (c[0] * uv[0] + c[1] * uv[1] + c[2] * uv[2]) / r.D;
+    r.dx = ((c[0] * vw[0] + c[1] * vw[1] + c[2] * vw[2]) / r.D) / r.g;
+    r.dy = ((c[0] * wu[0] + c[1] * wu[1] + c[2] * wu[2]) / r.D) / r.g;
+    return r;
+}
+
+// Returns false (and writes nothing) when the point does not land inside the image.
+SPC_CS_HD bool camera_splat(const float* eye, const float* U, const float* V, const float* W, int width, int height,
+                            const float* point, float& dx, float& dy, int& px, int& py, float& weight) {
+    const CameraProjection pr = camera_project(eye, U, V, W, point);
+    const float* c = pr.c;
+    const float D = pr.D, g = pr.g;
     if (!(g > 0.0f)) return false;
-    const float x = ((c[0] * vw[0] + c[1] * vw[1] + c[2] * vw[2]) / D) / g;
-    const float y = ((c[0] * wu[0] + c[1] * wu[1] + c[2] * wu[2]) / D) / g;
+    const float x = pr.dx, y = pr.dy;
     if (!(fabsf(x) < 1.0f && fabsf(y) < 1.0f)) return false;
     // (x + 1) may round up to 2 for x just below 1: the pixel index is clamped into the image
     int ix = (int)floorf((x + 1.0f) * 0.5f * (float)width), iy = (int)floorf((y + 1.0f) * 0.5f * (float)height);

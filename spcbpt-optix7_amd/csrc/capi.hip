@@ -367,6 +367,7 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     c->d_accum.release(); c->d_frame.release();
     c->free_features();           // feature buffers and denoiser planes of the old size: re-allocated on demand
     c->free_moments();            // ... and the film's second moment
+    c->free_history();            // ... and the history, its prior and the resolved image
     HIP_TRY(c, c->d_accum.reserve((size_t)w * h * 4));
     HIP_TRY(c, c->d_frame.reserve((size_t)w * h));
     for (auto& slots : c->d_result_b) for (auto& r : slots) r.release();   // re-allocated at the new size on demand

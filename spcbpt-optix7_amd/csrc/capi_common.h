@@ -3,6 +3,9 @@
 //   ctx_light.hip     Context: light passes (single / batched), the device sampler build (single / batched)
 //   ctx_exchange.hip  Context: the shards and imports of a sharded job (what libspcbpt_mgpu drives)
 //   ctx_render.hip    Context: eye / pt launches (single, deferred, batched), film merges
+//   ctx_features.hip  Context + extern "C": the first-hit feature pass and the a-trous denoiser
+//   ctx_moments.hip   Context + extern "C": the film's second moment, the film error, the variance-guided denoiser
+//   ctx_history.hip   Context + extern "C": history capture, reprojection into the current view, resolve
 //   capi.hip          extern "C": create / destroy, state, launches by name
 //   capi_exchange.hip extern "C": LVC export / import, film band packing
 //   capi_debug.hip    extern "C": read-backs, counters, timing, debug and test hooks, preprocessing entry points

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "layout.h"
+#include "reproject_pixel.h"   // ReprojectCamera: the history keeps the camera it was captured under
 
 namespace spc {
 
@@ -343,6 +344,20 @@ struct Context {
     int film_error(spcbpt_film_error_stats* out);
     int denoise_variance(const spcbpt_denoise_params& p);
     void free_moments();
+    // History reprojection (ctx_history.hip; spcbpt_history_*): H = (rgb, n) and G = (normal, depth) as captured, the prior R of the
+    // current view, the resolved image and its RGBA8 frame -- 68 B per pixel, allocated at the first capture after a resize or a reset
+    // (a resolve without a capture allocates the last two only), freed by spcbpt_resize and spcbpt_history_reset.
+    DevBuf<float> d_hist_rgbn, d_hist_normal_depth, d_prior, d_resolved;
+    DevBuf<uint32_t> d_resolved_frame;
+    ReprojectCamera hist_camera = {};
+    uint32_t hist_width = 0, hist_height = 0;
+    bool have_history = false, prior_live = false, have_resolved = false;
+    int history_ready(const char* what, bool need_features);
+    int resolve_into(uint32_t frames, float* out, uint32_t* frame);
+    int history_capture(uint32_t frames);
+    int history_reproject(const spcbpt_reproject_params& p);
+    int history_resolve(uint32_t frames);
+    void free_history();
     // preprocess.hip
     Preprocessor* pre = nullptr;
     spcbpt_pretrace_path* d_pre_paths = nullptr;

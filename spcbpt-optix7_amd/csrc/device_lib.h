@@ -253,6 +253,15 @@ SPC_DEV uint32_t quant8(float x) {
     x = clampf(x, 0.0f, 1.0f);
     return min((uint32_t)(x * 256.0f), 255u);
 }
+// the film's tone map of a radiance as RGBA8, the arithmetic of film_write below: for the image-space passes that show an image of
+// their own (k_remodulate, k_resolve)
+SPC_DEV uint32_t film_tone_map(f3 c) {
+    const float lum = 0.3f * c.x + 0.6f * c.y + 0.1f * c.z;
+    const float s = 1.0f / (1.0f + lum / 1.5f);
+    const f3 t = c * s;
+    return quant8(to_srgb(clampf(t.x, 0.f, 1.f))) | (quant8(to_srgb(clampf(t.y, 0.f, 1.f))) << 8) |
+           (quant8(to_srgb(clampf(t.z, 0.f, 1.f))) << 16) | (255u << 24);
+}
 SPC_DEV void film_store(float* buf, uint32_t width, uint32_t x, uint32_t y, f3 result) {  // radiance of one frame's sample
     reinterpret_cast<float4*>(buf)[(size_t)y * width + x] = make_float4(result.x, result.y, result.z, 1.0f);
 }

@@ -3,7 +3,8 @@
 //   kernels_light.hip    k_light_trace, the cache compaction, the shard / band packing of a sharded job
 //   kernels_sampler.hip  the device sampler build (MyThrustOp::LVC_Process), single and batched, both forms
 //   kernels_train.hip    the standalone traversal kernels and the pre-trace (TrainData) kernel
-// each with the launch_* functions kernels.h declares for its kernels).
+// each with the launch_* functions kernels.h declares for its kernels).  The image-space passes beside them bring launchers of their own:
+//   kernels_reproject.hip  k_reproject / k_resolve, the history reprojection (kernels_reproject.h)
 #pragma once
 #include "device_lib.h"
 #include "kernels.h"

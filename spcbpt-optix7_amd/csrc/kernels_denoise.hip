@@ -166,13 +166,7 @@ __global__ __launch_bounds__(BLOCK) void k_remodulate(const DenoiseParams p, con
     float o[3];
     denoise_remodulate(c3, b3, o);
     reinterpret_cast<float4*>(p.denoised)[idx] = make_float4(o[0], o[1], o[2], 1.0f);
-    // film_write's tone map (device_lib.h)
-    const f3 c = mk3(o[0], o[1], o[2]);
-    const float lum = 0.3f * c.x + 0.6f * c.y + 0.1f * c.z;
-    const float s = 1.0f / (1.0f + lum / 1.5f);
-    const f3 t = c * s;
-    p.frame[idx] = quant8(to_srgb(clampf(t.x, 0.f, 1.f))) | (quant8(to_srgb(clampf(t.y, 0.f, 1.f))) << 8) |
-                   (quant8(to_srgb(clampf(t.z, 0.f, 1.f))) << 16) | (255u << 24);
+    p.frame[idx] = film_tone_map(mk3(o[0], o[1], o[2]));   // film_write's tone map (device_lib.h)
 }
 
 void launch_demodulate(const DenoiseParams& p, hipStream_t s) {

@@ -139,6 +139,13 @@ struct spcbpt_viewer {
     uint32_t spec_subframe = 0;       // ... and subframe index
     long long frames = 0, spec_hits = 0, spec_drops = 0;
     int ctx_light_ahead_at_create = 0;   // the context's mode as the viewer found it: restored by spcbpt_viewer_destroy
+    // History reprojection (spcbpt_viewer_set_reproject, off by default): a frame that saw a camera change and nothing else captures
+    // what was shown under the old camera (spcbpt_history_capture) and reprojects it into the new view; every shown frame is
+    // followed by spcbpt_history_resolve, whose planes are what a front end then displays (spcbpt_read_history).
+    bool reproject = false;
+    bool reproject_restart = false;   // the switch was flipped: the next frame restarts the accumulation (and takes its features)
+    bool reproject_live = false;      // a prior is live on the context: the resolved image differs from the film
+    bool history_held = false;        // the context holds planes this viewer asked for since the last reset / resize
     void revalidate();
 };
 
@@ -169,6 +176,7 @@ void spc_viewers_forget_context(spcbpt_ctx* ctx) {
         if (v->ctx != ctx) continue;
         v->ctx = nullptr;
         v->light_pending = v->sampler_ready = v->spec_in_flight = false;
+        v->reproject_live = v->history_held = false;
     }
 }
 
@@ -334,13 +342,38 @@ int spcbpt_viewer_set_pipeline(spcbpt_viewer* v, int mode) {
 }
 int spcbpt_viewer_set_light_ahead(spcbpt_viewer* v, int on) { return spcbpt_viewer_set_pipeline(v, on ? 1 : 0); }   // (the round-3 name)
 
+// Flipping the switch drops the history and restarts the accumulation: the next frame is subframe 0 (and, switched on, takes the
+// features of its centre rays).  With a null context it is state only.
+int spcbpt_viewer_set_reproject(spcbpt_viewer* v, int on) {
+    if (!v) return SPCBPT_ERR_INVALID_ARG;
+    if ((on != 0) == v->reproject) return SPCBPT_OK;
+    if (v->ctx && v->history_held) {
+        const int rc = spcbpt_history_reset(v->ctx);   // (a frame traced ahead does not read the planes; the next frame drops it)
+        if (rc) return rc;
+    }
+    v->reproject = on != 0;
+    v->reproject_restart = true;
+    v->reproject_live = v->history_held = false;
+    return SPCBPT_OK;
+}
+int spcbpt_viewer_get_reproject(spcbpt_viewer* v, int* on, int* live) {
+    if (!v) return SPCBPT_ERR_INVALID_ARG;
+    if (on) *on = v->reproject ? 1 : 0;
+    if (live) *live = v->reproject_live ? 1 : 0;
+    return SPCBPT_OK;
+}
+
 // One pass of the render loop (791-822): updateState -> [SPCBPT_eye: launchLVCTrace] -> launchSubframe -> ++subframe_index.
 int spcbpt_viewer_frame(spcbpt_viewer* v) {
     if (!v) return SPCBPT_ERR_INVALID_ARG;
     const auto t0 = std::chrono::steady_clock::now();
     v->revalidate();
     // updateState (372-379)
-    const bool state_changed = v->camera_changed || v->resize_dirty || v->one_frame_render_only;   // what a frame traced ahead did not know
+    const bool state_changed = v->camera_changed || v->resize_dirty || v->one_frame_render_only || v->reproject_restart;   // what a frame traced ahead did not know
+    // the camera moved and nothing else happened, with at least one frame shown under the old camera: its image is carried over
+    const bool carry = v->reproject && v->camera_changed && !v->resize_dirty && !v->one_frame_render_only && !v->reproject_restart && v->subframe_index > 0;
+    const uint32_t shown = v->subframe_index;
+    v->reproject_restart = false;
     if (state_changed) v->subframe_index = 0;
     int rc = SPCBPT_OK;
     // the frame traced ahead: still this frame, or overtaken by an event (dropped before the size or the camera change)
@@ -348,6 +381,18 @@ int spcbpt_viewer_frame(spcbpt_viewer* v) {
     if (v->spec_in_flight && v->ctx) {
         have = !state_changed && v->spec_alg == v->render_alg_id && v->spec_subframe == v->subframe_index;
         if (!have) { v->spec_in_flight = false; v->spec_drops++; rc = spcbpt_merge_deferred(v->ctx, 0); if (rc) return rc; }   // (whatever the call says, the context holds no deferred frame afterwards)
+    }
+    if (v->reproject && v->ctx && state_changed) {
+        if (carry) {   // before the camera changes: what has been shown so far, with the camera it was shown under
+            rc = spcbpt_history_capture(v->ctx, shown);
+            if (rc) return rc;
+            v->history_held = true;
+        } else if (v->history_held) {   // a resize, an algorithm switch, a restart: the history describes another film
+            rc = spcbpt_history_reset(v->ctx);
+            if (rc) return rc;
+            v->history_held = false;
+        }
+        v->reproject_live = false;
     }
     if (v->camera_changed) {  // handleCameraUpdate (352-370)
         v->camera_changed = false;
@@ -385,6 +430,18 @@ int spcbpt_viewer_frame(spcbpt_viewer* v) {
             if (rc) return rc;
         }
         if (spcbpt) v->sampler_ready = false;   // consumed by the frame being shown
+        if (v->reproject) {   // behind the shown frame's merge, in front of a deferred launch (the history calls refuse while one is outstanding)
+            if (v->subframe_index == 0) { rc = spcbpt_launch_features(v->ctx, 0, 0, v->height, 1); if (rc) return rc; }   // centre rays: the first hits exactly
+            if (carry) {
+                const spcbpt_reproject_params defaults = {0.0f, 0.0f, 0.0f};
+                rc = spcbpt_history_reproject(v->ctx, &defaults);
+                if (rc) return rc;
+                v->reproject_live = true;
+            }
+            rc = spcbpt_history_resolve(v->ctx, v->subframe_index + 1);
+            if (rc) return rc;
+            v->history_held = true;
+        }
         // ---- ahead of the display
         // Mode 2 speculates only from a steady view: a call that itself saw an event (a drag in progress, a resize, a key) is likely to
         // be followed by another, the frame queued here would be dropped by it -- after running to completion beside the real frame,
