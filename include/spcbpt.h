@@ -591,8 +591,9 @@ int spcbpt_reproject_params_struct_size(void);   /* sizeof(spcbpt_reproject_para
  * The intended sequence: capture at the old camera, spcbpt_set_camera, spcbpt_launch(alg, 0), spcbpt_launch_features(0), reproject,
  * then resolve(1), spcbpt_launch(alg, 1), resolve(2), ...  The features of both views should be those of subframe 0 (centre rays:
  * P is then the first hit exactly); later feature means still work, they only blur P by the jitter.
- * Not covered: sky pixels (a miss has no depth), the moments plane and spcbpt_film_error (they keep describing the film), sharded
- * films, the batched and deferred launch forms, moving geometry.  A reprojected highlight lags for up to max_history frames. */
+ * Not covered: sky pixels (a miss has no depth), spcbpt_film_error on the resolved image (it and the moments plane keep describing
+ * the film; the variance of the resolved image is spcbpt_read_history_variance's), sharded films, the batched and deferred launch
+ * forms, moving geometry.  A reprojected highlight lags for up to max_history frames. */
 int spcbpt_history_capture(spcbpt_ctx* ctx, uint32_t frames);
 int spcbpt_history_reproject(spcbpt_ctx* ctx, const spcbpt_reproject_params* params);
 int spcbpt_history_resolve(spcbpt_ctx* ctx, uint32_t frames);
@@ -610,6 +611,57 @@ int spcbpt_history_reproject_host(const float eye[3], const float U[3], const fl
                                   const float* history_normal_depth_rgba, const float* history_rgbn, int width, int height,
                                   const spcbpt_reproject_params* params, float sigma_x_default_diag, float* prior_out);
 int spcbpt_history_resolve_host(const float* prior_rgba, const float* accum_rgba, uint32_t frames, int64_t n_pixels, float* out_rgba);
+
+/* The variance of what is shown, carried through the history, and the variance-guided denoiser on the resolved image (no reference
+ * counterpart), opt-in.  "Variance" is the per-channel variance of the MEAN of a pixel, in a float4 plane (V_r, V_g, V_b, 0) in the
+ * film's row order; float32 without contraction throughout.
+ * Film variance VA(p), from accum and the moments plane m2n = (M2, n) (a plane that does not exist yet counts as n = 0 everywhere):
+ *   n >= 2:  VA_k = max(M2_k, 0) / (n (n - 1))      (the operations of sd_k above before its square root: sqrtf(VA_k) is sd_k bit for bit)
+ *   n <  2:  VA_k = accum_k^2                       (unknown variance: as uncertain as its own value, per channel; the one branch, on the integer n)
+ * History variance HV(q): the variance of H(q).rgb, taken at capture.
+ * Prior variance PV(p): the reprojection's own taps, weights w_q and sum S with HV as the payload,
+ *   PV_k = sum_q w_q HV_k(q) / S,      0 wherever R(p) = 0 (a miss, g <= 0, S < 1e-6)
+ * -- linear in the variance, not w_q^2: neighbouring history pixels share light sub-paths and the taps of earlier interpolations, so
+ * they are not independent and the w^2 rule would understate the variance.  max_history clamps what the prior is worth (m), not how
+ * uncertain its value is: PV is not rescaled by it.
+ * Resolved variance RV(p), with m = R(p).w and Nf = (float)frames as in the resolve:
+ *   RV_k = (m^2 PV_k + Nf^2 VA_k) / (m + Nf)^2;      while no prior is live RV = VA bit for bit (the value, not the formula with m = 0)
+ * VA uses the moments plane's own n; `frames` only weights, as in the blend.  Capture: HV becomes the RV of the capture's resolve (a
+ * live prior is folded in, so a chain of moves keeps its variance as H keeps its history).
+ * The history carries variance exactly while the moments switch (spcbpt_set_film_moments) is on: a capture made then also writes HV,
+ * a reproject of a history that has HV also writes PV (one pass, the weights computed once), a resolve made then also writes RV -- a
+ * live prior has to have PV for that.  Prior, resolved image and RGBA8 frame are the same bits either way; with the switch off the
+ * calls run the kernels they always ran and no variance plane counts as valid.  Three more float4 planes, 48 B per pixel, each
+ * allocated by the first call that writes it, freed with the history planes; switching the moments off invalidates them.
+ * History denoise: the iterations, guides, step parameters, remodulation and output planes of spcbpt_denoise_variance (read with
+ * spcbpt_read_denoised), started from the resolved image (w = (0.3, 0.6, 0.1)):
+ *   c_0(p) = resolved(p).rgb / max(albedo(p).rgb, 1e-3)
+ *   v_0(p) = (sum_k w_k sqrtf(RV_k(p)) / max(albedo_k(p), 1e-3))^2
+ * so a re-used pixel is filtered as narrowly as its history deserves and a disoccluded one as widely as its single sample needs.  On
+ * a film whose pixels all have n >= 2, with no prior live, the output is spcbpt_denoise_variance's bit for bit.  sigma_c is read as
+ * sigma_v; defaults and argument checks are spcbpt_denoise_variance's.  A link of the film-merge chain, asynchronous; the kernel-time
+ * span is "history_denoise".  Needs a feature launch since the last spcbpt_resize, a resolve that produced RV since the last resize
+ * or reset, and no deferred frame outstanding (else SPCBPT_ERR_STATE, with text).  Writes the denoiser's planes only.
+ * Not covered: sky pixels, spcbpt_film_error on the resolved image, sharded films and the N-GPU host, the batched and deferred
+ * launch forms, a specular / diffuse split, temporal accumulation of per-sample moments (SVGF's way of steadying a 2-frame variance). */
+int spcbpt_history_denoise(spcbpt_ctx* ctx, const spcbpt_denoise_params* params);
+/* Waits like spcbpt_read_history and copies RV, PV and HV (any pointer may be NULL).  SPCBPT_ERR_STATE for a plane that is not valid:
+ * nothing resolved / no live prior / nothing captured, or the moments were off when it was. */
+int spcbpt_read_history_variance(spcbpt_ctx* ctx, float* resolved_var, float* prior_var, float* history_var);
+/* The same per-pixel functions on caller buffers on the host; no context and no GPU needed.  The reprojection takes
+ * spcbpt_history_reproject_host's arguments plus HV and the plane for PV (prior_out is that call's, bit for bit); the resolve's
+ * prior_rgba and prior_var are both NULL (no prior) or both given; the denoise takes the resolved image and RV with the feature
+ * planes as spcbpt_denoise_variance_host does.  SPCBPT_ERR_INVALID_ARG as for their siblings. */
+int spcbpt_history_reproject_var_host(const float eye[3], const float U[3], const float V[3], const float W[3], const float* normal_depth_rgba,
+                                      const float eye_h[3], const float U_h[3], const float V_h[3], const float W_h[3],
+                                      const float* history_normal_depth_rgba, const float* history_rgbn, const float* history_var,
+                                      int width, int height, const spcbpt_reproject_params* params, float sigma_x_default_diag,
+                                      float* prior_out, float* prior_var_out);
+int spcbpt_history_resolve_var_host(const float* prior_rgba, const float* prior_var, const float* accum_rgba, const float* m2n, uint32_t frames,
+                                    int64_t n_pixels, float* out_rgba, float* out_var);
+int spcbpt_history_denoise_host(const float* resolved_rgba, const float* resolved_var, const float* albedo_rgba, const float* normal_depth_rgba,
+                                const float eye[3], const float U[3], const float V[3], const float W[3],
+                                int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
 
 int spcbpt_get_counters(spcbpt_ctx* ctx, spcbpt_counters* out);
 int spcbpt_reset_counters(spcbpt_ctx* ctx);
@@ -955,6 +1007,13 @@ int spcbpt_viewer_set_light_ahead(spcbpt_viewer* v, int on);
  * only.  `live` tells whether a prior is live on the context, i.e. whether the resolved image differs from the film. */
 int spcbpt_viewer_set_reproject(spcbpt_viewer* v, int on);
 int spcbpt_viewer_get_reproject(spcbpt_viewer* v, int* on, int* live);
+/* Denoising what the loop shows (spcbpt_history_denoise; off by default).  Needs the reproject switch on (else SPCBPT_ERR_STATE);
+ * switching reproject off switches it off.  Switching it on switches the context's film moments on, switching it off restores what
+ * it found; flipping it restarts the accumulation like spcbpt_viewer_set_reproject.  While on, every shown frame's
+ * spcbpt_history_resolve is followed by spcbpt_history_denoise with the default parameters (in every pipeline mode in front of the
+ * deferred launch), and what to display is spcbpt_read_denoised.  The film is what it always was. */
+int spcbpt_viewer_set_denoise(spcbpt_viewer* v, int on);
+int spcbpt_viewer_get_denoise(spcbpt_viewer* v, int* on);
 int spcbpt_viewer_frame(spcbpt_viewer* v);
 int spcbpt_viewer_get_state(spcbpt_viewer* v, spcbpt_viewer_state* state);
 const char* spcbpt_viewer_alg_name(int alg_id);

@@ -419,6 +419,65 @@ def history_resolve_host(prior, accum, frames):
     return out
 
 
+def history_reproject_var_host(camera, normal_depth, history_camera, history_normal_depth, history_rgbn, history_var, sigma_n=0.0, sigma_x=0.0, max_history=0.0, diag=0.0):
+    """spcbpt_history_reproject_var_host: history_reproject_host with the history's variance plane `history_var` ((h, w, 4): the
+    per-channel variance of history_rgbn's rgb) as a second payload of the same taps.  Returns (prior, prior_var): the (h, w, 4) prior
+    (rgb, m), bit for bit history_reproject_host's, and its variance (V_r, V_g, V_b, 0).  No GPU needed; the inputs are not written."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (normal_depth, history_normal_depth, history_rgbn, history_var)]
+    h, w = a[0].shape[:2]
+    if any(v.shape != (h, w, 4) for v in a):
+        raise SpcbptError("history_reproject_var_host: the four planes must be (h, w, 4) arrays of one size")
+    cam = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in tuple(camera) + tuple(history_camera)]
+    if len(cam) != 8:
+        raise SpcbptError("history_reproject_var_host: a camera is (eye, U, V, W)")
+    out, out_var = np.zeros((h, w, 4), dtype=np.float32), np.zeros((h, w, 4), dtype=np.float32)
+    p = ReprojectParams(float(sigma_n), float(sigma_x), float(max_history))
+    rc = lib.spcbpt_history_reproject_var_host(*[_fp(v) for v in cam[:4]], _fp(a[0]), *[_fp(v) for v in cam[4:]], _fp(a[1]), _fp(a[2]), _fp(a[3]), w, h,
+                                               C.byref(p), C.c_float(diag), _fp(out), _fp(out_var))
+    if rc != 0:
+        raise SpcbptError(f"history_reproject_var_host failed ({rc})")
+    return out, out_var
+
+
+def history_resolve_var_host(prior, prior_var, accum, m2n, frames):
+    """spcbpt_history_resolve_var_host: history_resolve_host with the variance of the blend -- the prior and its variance (both None: no
+    prior), the film's mean of `frames` frames and its moments plane as read_film_moments gives it.  Returns (resolved, resolved_var):
+    (rgb, m + frames) and (V_r, V_g, V_b, 0).  No GPU needed."""
+    lib = load_library()
+    a, m = (np.ascontiguousarray(v, dtype=np.float32) for v in (accum, m2n))
+    r = None if prior is None else np.ascontiguousarray(prior, dtype=np.float32)
+    rv = None if prior_var is None else np.ascontiguousarray(prior_var, dtype=np.float32)
+    if a.shape[-1] != 4 or m.shape != a.shape or any(v is not None and v.shape != a.shape for v in (r, rv)):
+        raise SpcbptError("history_resolve_var_host: the planes must be (..., 4) arrays of one shape")
+    if int(frames) < 0 or int(frames) >= 2**32:
+        raise SpcbptError("history_resolve_var_host: frames out of range")
+    out, out_var = np.zeros(a.shape, dtype=np.float32), np.zeros(a.shape, dtype=np.float32)
+    rc = lib.spcbpt_history_resolve_var_host(_fp(r) if r is not None else None, _fp(rv) if rv is not None else None, _fp(a), _fp(m), int(frames), a.size // 4,
+                                             _fp(out), _fp(out_var))
+    if rc != 0:
+        raise SpcbptError(f"history_resolve_var_host failed ({rc})")
+    return out, out_var
+
+
+def history_denoise_host(resolved, resolved_var, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_v=0.0, sigma_n=0.0, sigma_x=0.0):
+    """spcbpt_history_denoise_host: the variance-guided a-trous denoiser of Renderer.history_denoise on (h, w, 4) float32 arrays as
+    read_history / read_history_variance / read_features give them.  Host code in float32 -- the per-pixel function the kernels run; no
+    GPU needed.  A sigma <= 0 takes its default.  Returns the denoised (h, w, 4) image; the inputs are not written."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (resolved, resolved_var, albedo, normal_depth)]
+    h, w = a[0].shape[:2]
+    if any(v.shape != (h, w, 4) for v in a):
+        raise SpcbptError("history_denoise_host: resolved, resolved_var, albedo and normal_depth must be (h, w, 4) arrays of one size")
+    cam = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W)]
+    out = np.zeros((h, w, 4), dtype=np.float32)
+    p = DenoiseParams(int(iterations), float(sigma_v), float(sigma_n), float(sigma_x))
+    rc = lib.spcbpt_history_denoise_host(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), *[_fp(v) for v in cam], w, h, C.byref(p), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"history_denoise_host failed ({rc})")
+    return out
+
+
 def film_moments_update_host(mean_before, sample, subframe, m2n):
     """spcbpt_film_moments_update_host: one merge's update of the moment plane `m2n` ((..., 4) float32, C-contiguous, updated IN PLACE)
     from the film before the merge and the frame's samples (same shape).  The per-pixel function the kernel runs; no GPU needed."""
@@ -537,6 +596,16 @@ class Viewer:
         on, live = C.c_int32(), C.c_int32()
         self._chk(self.lib.spcbpt_viewer_get_reproject(self.h, C.byref(on), C.byref(live)), "viewer_get_reproject")
         return {"on": int(on.value), "live": int(live.value)}
+
+    def set_denoise(self, on):
+        """spcbpt_viewer_set_denoise: follow every shown frame's resolve with history_denoise (defaults); display read_denoised().  Needs
+        set_reproject(True); switches the context's film moments on (and back); flipping it restarts the accumulation."""
+        self._chk(self.lib.spcbpt_viewer_set_denoise(self.h, int(bool(on))), "viewer_set_denoise")
+
+    def get_denoise(self) -> bool:
+        on = C.c_int32()
+        self._chk(self.lib.spcbpt_viewer_get_denoise(self.h, C.byref(on)), "viewer_get_denoise")
+        return bool(on.value)
 
     def set_pipeline(self, mode: int):
         """0 the reference's order, 1 next light pass beside the eye kernel, 2 (default) next frame traced while this one is shown."""
@@ -739,6 +808,11 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_history_reset": [vp], "spcbpt_reproject_params_struct_size": [], "spcbpt_read_history": [vp, vp, vp, vp, vp],
         "spcbpt_history_reproject_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(ReprojectParams), C.c_float, f32p],
         "spcbpt_history_resolve_host": [f32p, f32p, C.c_uint32, C.c_int64, f32p],
+        "spcbpt_history_denoise": [vp, C.POINTER(DenoiseParams)], "spcbpt_read_history_variance": [vp, vp, vp, vp],
+        "spcbpt_history_reproject_var_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(ReprojectParams), C.c_float, f32p, f32p],
+        "spcbpt_history_resolve_var_host": [f32p, f32p, f32p, f32p, C.c_uint32, C.c_int64, f32p, f32p],
+        "spcbpt_history_denoise_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
+        "spcbpt_viewer_set_denoise": [vp, i32], "spcbpt_viewer_get_denoise": [vp, C.POINTER(i32)],
         "spcbpt_viewer_set_reproject": [vp, i32], "spcbpt_viewer_get_reproject": [vp, C.POINTER(i32), C.POINTER(i32)],
         "spcbpt_denoise_variance_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p],
         "spcbpt_preprocess": [vp, i32, i32, i32],
@@ -806,6 +880,8 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
     "spcbpt_history_reproject_host", "spcbpt_history_resolve_host", "spcbpt_viewer_set_reproject", "spcbpt_viewer_get_reproject",
+    "spcbpt_history_denoise", "spcbpt_read_history_variance", "spcbpt_history_reproject_var_host", "spcbpt_history_resolve_var_host", "spcbpt_history_denoise_host",
+    "spcbpt_viewer_set_denoise", "spcbpt_viewer_get_denoise",
     "spcbpt_preprocess", "spcbpt_get_subspace", "spcbpt_scene_info", "spcbpt_set_pretrace", "spcbpt_train_records_count",
     "spcbpt_train_records_read", "spcbpt_train_records_import", "spcbpt_train_records_clear", "spcbpt_preprocess_stage",
     "spcbpt_get_gamma", "spcbpt_gltf_load", "spcbpt_scene_file_load", "spcbpt_scene_file_desc", "spcbpt_scene_file_camera",
@@ -1059,6 +1135,22 @@ class Renderer:
     def history_resolve(self, frames):
         """spcbpt_history_resolve: the prior (if one is live) blended with the film's mean of `frames` frames; read with read_history()."""
         self._chk(self.lib.spcbpt_history_resolve(self.h, int(frames)), "history_resolve")
+
+    def history_denoise(self, iterations=5, sigma_v=0.0, sigma_n=0.0, sigma_x=0.0):
+        """spcbpt_history_denoise: denoise_variance's filter on the resolved image, guided by the variance the history carries (the
+        moments on from the capture on: set_film_moments(True); launch_features and history_resolve first).  A sigma <= 0 takes its
+        default.  The result is read with read_denoised(); film and history planes are not touched."""
+        p = DenoiseParams(int(iterations), float(sigma_v), float(sigma_n), float(sigma_x))
+        self._chk(self.lib.spcbpt_history_denoise(self.h, C.byref(p)), "history_denoise")
+
+    def read_history_variance(self, resolved=True, prior=False, history=False):
+        """spcbpt_read_history_variance: a dict of the (h, w, 4) float32 variance planes asked for -- (V_r, V_g, V_b, 0), the variance of
+        the mean -- of the "resolved" image, the "prior", the captured "history".  SpcbptError (-5) for a plane that is not valid."""
+        w, h = self.image_size()
+        want = {"resolved": resolved, "prior": prior, "history": history}
+        out = {k: np.zeros((h, w, 4), dtype=np.float32) for k, on in want.items() if on}
+        self._chk(self.lib.spcbpt_read_history_variance(self.h, *[out[k].ctypes.data if k in out else None for k in want]), "read_history_variance")
+        return out
 
     def history_reset(self):
         self._chk(self.lib.spcbpt_history_reset(self.h), "history_reset")

@@ -353,11 +353,19 @@ struct Context {
     uint32_t hist_width = 0, hist_height = 0;
     bool have_history = false, prior_live = false, have_resolved = false;
     int history_ready(const char* what, bool need_features);
-    int resolve_into(uint32_t frames, float* out, uint32_t* frame);
+    int resolve_into(uint32_t frames, float* out, uint32_t* frame, float* out_var = nullptr);   // out_var: the variance-carrying kernel
     int history_capture(uint32_t frames);
     int history_reproject(const spcbpt_reproject_params& p);
     int history_resolve(uint32_t frames);
     void free_history();
+    // The variance of what is shown (spcbpt_history_denoise): HV, PV and RV, one float4 plane (V_r, V_g, V_b, 0) beside H, the prior and
+    // the resolved image -- 48 B per pixel more, each allocated at the first call that writes it.  The history carries variance exactly
+    // while the moments switch is on: a capture then writes HV, a reproject of a history with HV writes PV, a resolve writes RV.
+    // Freed with the history planes; the flags fall with have_history / prior_live / have_resolved and with the moments switch.
+    DevBuf<float> d_hist_var, d_prior_var, d_resolved_var;
+    bool have_hist_var = false, have_prior_var = false, have_resolved_var = false;
+    bool history_variance_now() const;   // the call being made carries variance
+    int history_denoise(const spcbpt_denoise_params& p);
     // preprocess.hip
     Preprocessor* pre = nullptr;
     spcbpt_pretrace_path* d_pre_paths = nullptr;

@@ -17,6 +17,7 @@ int Context::set_film_moments(bool on) {
     if (!on) {   // the plane goes with the switch: merges that still read it may be queued
         if (sync_all()) return SPCBPT_ERR_HIP;
         free_moments();
+        have_hist_var = have_prior_var = have_resolved_var = false;   // the history's variance goes with the switch (its planes stay until the history's go)
     }
     film_moments = on;
     return 0;

@@ -1,4 +1,5 @@
-// spcbpt_denoise_host / spcbpt_denoise_variance_host: the denoisers of spcbpt_denoise / spcbpt_denoise_variance on caller buffers, on
+// spcbpt_denoise_host / spcbpt_denoise_variance_host / spcbpt_history_denoise_host: the denoisers of spcbpt_denoise /
+// spcbpt_denoise_variance / spcbpt_history_denoise on caller buffers, on
 // the host -- denoise_pixel.h, the header the kernels of kernels_denoise.hip run, over plain arrays.  No context, no GPU (plain g++,
 // -ffp-contract=off like the device code).
 #include <cstring>
@@ -47,19 +48,12 @@ float host_guides(const float* accum_rgba, const float* albedo_rgba, const float
     return sqrtf((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
 }
 
-}  // namespace
-
-extern "C" int spcbpt_denoise_variance_host(const float* accum_rgba, const float* m2n, const float* albedo_rgba, const float* normal_depth_rgba,
-                                            const float eye[3], const float U[3], const float V[3], const float W[3],
-                                            int width, int height, const spcbpt_denoise_params* p, float* out_rgba) {
+// the iterations and the remodulation both variance-guided forms share: c, v are the start values
+int host_variance_filter(std::vector<float>& c, std::vector<float>& v, const std::vector<float>& n, const std::vector<float>& X, float diag,
+                         const float* albedo_rgba, int width, int height, const spcbpt_denoise_params* p, float* out_rgba) {
     using namespace spc;
-    if (!accum_rgba || !m2n || !albedo_rgba || !normal_depth_rgba || !eye || !U || !V || !W || !p || !out_rgba) return SPCBPT_ERR_INVALID_ARG;
-    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) return SPCBPT_ERR_INVALID_ARG;
-    if (p->iterations < 1 || p->iterations > kDenoiseMaxIterations) return SPCBPT_ERR_INVALID_ARG;
     const size_t px = (size_t)width * height;
-    std::vector<float> c(px * 3), c2(px * 3), n(px * 3), X(px * 3), v(px), v2(px);
-    const float diag = host_guides(accum_rgba, albedo_rgba, normal_depth_rgba, U, V, W, width, height, c, n, X);
-    for (size_t i = 0; i < px; i++) v[i] = denoise_variance_start(&c[i * 3], albedo_rgba + i * 4, m2n + i * 4);
+    std::vector<float> c2(px * 3), v2(px);
     const float sigma_v = p->sigma_c > 0.0f ? p->sigma_c : SPCBPT_DENOISE_SIGMA_V;
     const float sigma_n = p->sigma_n > 0.0f ? p->sigma_n : SPCBPT_DENOISE_SIGMA_N;
     const float sigma_x = p->sigma_x > 0.0f ? p->sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
@@ -83,6 +77,37 @@ extern "C" int spcbpt_denoise_variance_host(const float* accum_rgba, const float
         out_rgba[i * 4 + 3] = 1.0f;
     }
     return SPCBPT_OK;
+}
+
+}  // namespace
+
+extern "C" int spcbpt_denoise_variance_host(const float* accum_rgba, const float* m2n, const float* albedo_rgba, const float* normal_depth_rgba,
+                                            const float eye[3], const float U[3], const float V[3], const float W[3],
+                                            int width, int height, const spcbpt_denoise_params* p, float* out_rgba) {
+    using namespace spc;
+    if (!accum_rgba || !m2n || !albedo_rgba || !normal_depth_rgba || !eye || !U || !V || !W || !p || !out_rgba) return SPCBPT_ERR_INVALID_ARG;
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) return SPCBPT_ERR_INVALID_ARG;
+    if (p->iterations < 1 || p->iterations > kDenoiseMaxIterations) return SPCBPT_ERR_INVALID_ARG;
+    const size_t px = (size_t)width * height;
+    std::vector<float> c(px * 3), n(px * 3), X(px * 3), v(px);
+    const float diag = host_guides(accum_rgba, albedo_rgba, normal_depth_rgba, U, V, W, width, height, c, n, X);
+    for (size_t i = 0; i < px; i++) v[i] = denoise_variance_start(&c[i * 3], albedo_rgba + i * 4, m2n + i * 4);
+    return host_variance_filter(c, v, n, X, diag, albedo_rgba, width, height, p, out_rgba);
+}
+
+// spcbpt_history_denoise on the host: the same filter from the resolved image and its per-channel variance
+extern "C" int spcbpt_history_denoise_host(const float* resolved_rgba, const float* resolved_var, const float* albedo_rgba, const float* normal_depth_rgba,
+                                           const float eye[3], const float U[3], const float V[3], const float W[3],
+                                           int width, int height, const spcbpt_denoise_params* p, float* out_rgba) {
+    using namespace spc;
+    if (!resolved_rgba || !resolved_var || !albedo_rgba || !normal_depth_rgba || !eye || !U || !V || !W || !p || !out_rgba) return SPCBPT_ERR_INVALID_ARG;
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) return SPCBPT_ERR_INVALID_ARG;
+    if (p->iterations < 1 || p->iterations > kDenoiseMaxIterations) return SPCBPT_ERR_INVALID_ARG;
+    const size_t px = (size_t)width * height;
+    std::vector<float> c(px * 3), n(px * 3), X(px * 3), v(px);
+    const float diag = host_guides(resolved_rgba, albedo_rgba, normal_depth_rgba, U, V, W, width, height, c, n, X);
+    for (size_t i = 0; i < px; i++) v[i] = denoise_resolved_start(albedo_rgba + i * 4, resolved_var + i * 4);
+    return host_variance_filter(c, v, n, X, diag, albedo_rgba, width, height, p, out_rgba);
 }
 
 extern "C" int spcbpt_denoise_host(const float* accum_rgba, const float* albedo_rgba, const float* normal_depth_rgba,

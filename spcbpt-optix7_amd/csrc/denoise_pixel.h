@@ -117,6 +117,17 @@ SPC_DN_HD float denoise_variance_start(const float* c0, const float* albedo, con
     }
     return s * s;
 }
+// v_0(p) of the resolved image (spcbpt_history_denoise) from its per-channel variance RV (reproject_pixel.h: resolve_var_pixel):
+//   (sum_k w_k sqrtf(RV_k) / max(albedo_k, 1e-3))^2
+// the n >= 2 line above with sqrtf(RV_k) for sd_k, in its order -- where RV is the film's own variance of a pixel with n >= 2,
+// sqrtf(RV_k) is sd_k and the value is denoise_variance_start's bit for bit.  No branch.
+SPC_DN_HD float denoise_resolved_start(const float* albedo, const float* rv) {
+    float sd[3];
+    for (int k = 0; k < 3; k++) sd[k] = sqrtf(rv[k]);
+    for (int k = 0; k < 3; k++) sd[k] = sd[k] / fmaxf(albedo[k], kDenoiseAlbedoFloor);
+    const float s = denoise_luminance(sd);
+    return s * s;
+}
 
 // One pixel of one iteration of the variance-guided filter.  `F` is atrous_pixel's, plus   float F::variance(int x, int y) const
 //   v~(p)   = the (1/4, 1/2, 1/4)^2 mean of v over the 3 x 3 neighbours of p at distance 1 inside the image, renormalised

@@ -26,5 +26,7 @@ void launch_remodulate(const DenoiseParams& p, bool from_pong, hipStream_t s);  
 // the variance-guided form (spcbpt_denoise_variance): the variance rides in the .w of ping / pong; launch_remodulate ends it too
 void launch_demodulate_var(const DenoiseParams& p, const float* m2n, hipStream_t s);                      // accum, features, moments -> ping, position
 void launch_atrous_var(const DenoiseParams& p, const AtrousVarStep& a, bool ping_to_pong, hipStream_t s); // one iteration
+// spcbpt_history_denoise: the same start planes from the resolved image (in p.accum's place) and its variance plane; launch_atrous_var / launch_remodulate go on
+void launch_demodulate_resolved(const DenoiseParams& p, const float* resolved_var, hipStream_t s);
 
 }  // namespace spc

@@ -1,7 +1,8 @@
 // The edge-avoiding a-trous denoiser on the demodulated film (spcbpt_denoise): k_demodulate divides the film by the first-hit albedo
 // and turns depth into a position, k_atrous runs one iteration of the filter (denoise_pixel.h, the function spcbpt_denoise_host
 // runs on the host) from one float4 plane into the other, k_remodulate multiplies the albedo back and tone-maps.
-// k_demodulate_var / k_atrous_var / k_atrous_var_lds are the variance-guided form (spcbpt_denoise_variance) between the same planes.
+// k_demodulate_var / k_atrous_var / k_atrous_var_lds are the variance-guided form (spcbpt_denoise_variance) between the same planes;
+// k_demodulate_resolved starts that form from the resolved image of the history reprojection (spcbpt_history_denoise).
 // (kernel_config.h maps the other kernel files)
 #include <hip/hip_runtime.h>
 
@@ -112,6 +113,20 @@ __global__ __launch_bounds__(BLOCK) void k_demodulate_var(const DenoiseParams p,
     reinterpret_cast<float4*>(p.position)[idx] = make_float4(X[0], X[1], X[2], 0.0f);
 }
 
+// spcbpt_history_denoise: the start planes from the resolved image (p.accum) and its per-channel variance RV instead of film and moments
+__global__ __launch_bounds__(BLOCK) void k_demodulate_resolved(const DenoiseParams p, const float* __restrict__ resolved_var) {
+    int x, y;
+    if (!denoise_pixel_of_lane(p, x, y)) return;
+    const size_t idx = (size_t)y * p.width + x;
+    const float4 res = ldq(p.accum, idx), alb = ldq(p.albedo, idx), nd = ldq(p.normal_depth, idx), rv = ldq(resolved_var, idx);
+    const float a3[3] = {res.x, res.y, res.z}, b3[3] = {alb.x, alb.y, alb.z}, v3[3] = {rv.x, rv.y, rv.z};
+    float c[3], X[3];
+    denoise_demodulate(a3, b3, c);
+    denoise_position(p.U, p.V, p.W, (int)p.width, (int)p.height, x, y, nd.w, X);
+    reinterpret_cast<float4*>(p.ping)[idx] = make_float4(c[0], c[1], c[2], denoise_resolved_start(b3, v3));
+    reinterpret_cast<float4*>(p.position)[idx] = make_float4(X[0], X[1], X[2], 0.0f);
+}
+
 struct GlobalVarPlanes : GlobalPlanes {   // atrous_var_pixel's F over the global float4 planes: v is c's .w
     SPC_DEV float variance(int x, int y) const { return c[((size_t)y * width + x) * 4 + 3]; }
 };
@@ -182,6 +197,9 @@ void launch_atrous(const DenoiseParams& p, const AtrousStep& a, bool ping_to_pon
 }
 void launch_demodulate_var(const DenoiseParams& p, const float* m2n, hipStream_t s) {
     hipLaunchKernelGGL(k_demodulate_var, denoise_grid(p), dim3(BLOCK), 0, s, p, m2n);
+}
+void launch_demodulate_resolved(const DenoiseParams& p, const float* resolved_var, hipStream_t s) {
+    hipLaunchKernelGGL(k_demodulate_resolved, denoise_grid(p), dim3(BLOCK), 0, s, p, resolved_var);
 }
 void launch_atrous_var(const DenoiseParams& p, const AtrousVarStep& a, bool ping_to_pong, hipStream_t s) {
     const float* src = ping_to_pong ? p.ping : p.pong;

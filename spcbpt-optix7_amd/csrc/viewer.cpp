@@ -146,6 +146,11 @@ struct spcbpt_viewer {
     bool reproject_restart = false;   // the switch was flipped: the next frame restarts the accumulation (and takes its features)
     bool reproject_live = false;      // a prior is live on the context: the resolved image differs from the film
     bool history_held = false;        // the context holds planes this viewer asked for since the last reset / resize
+    // Denoising what is shown (spcbpt_viewer_set_denoise, off by default; needs `reproject`): every shown frame's resolve is followed
+    // by spcbpt_history_denoise with the defaults, whose planes a front end then displays (spcbpt_read_denoised).  The variance it
+    // filters by needs the context's film moments, which the switch turns on and puts back as it found them.
+    bool denoise = false;
+    int ctx_moments_before_denoise = 0;
     void revalidate();
 };
 
@@ -220,6 +225,7 @@ void spcbpt_viewer_destroy(spcbpt_viewer* v) {
     if (v->ctx) {
         int deferred = 0;
         if (!spcbpt_get_pipeline_state(v->ctx, nullptr, nullptr, nullptr, &deferred) && deferred) (void)spcbpt_merge_deferred(v->ctx, 0);
+        if (v->denoise) (void)spcbpt_set_film_moments(v->ctx, v->ctx_moments_before_denoise);
         (void)spcbpt_set_light_ahead(v->ctx, v->ctx_light_ahead_at_create);   // (waits for what is queued; clears the pending passes)
     }
     {
@@ -347,6 +353,7 @@ int spcbpt_viewer_set_light_ahead(spcbpt_viewer* v, int on) { return spcbpt_view
 int spcbpt_viewer_set_reproject(spcbpt_viewer* v, int on) {
     if (!v) return SPCBPT_ERR_INVALID_ARG;
     if ((on != 0) == v->reproject) return SPCBPT_OK;
+    if (!on && v->denoise) { const int rc = spcbpt_viewer_set_denoise(v, 0); if (rc) return rc; }   // no resolved image, nothing to denoise
     if (v->ctx && v->history_held) {
         const int rc = spcbpt_history_reset(v->ctx);   // (a frame traced ahead does not read the planes; the next frame drops it)
         if (rc) return rc;
@@ -360,6 +367,36 @@ int spcbpt_viewer_get_reproject(spcbpt_viewer* v, int* on, int* live) {
     if (!v) return SPCBPT_ERR_INVALID_ARG;
     if (on) *on = v->reproject ? 1 : 0;
     if (live) *live = v->reproject_live ? 1 : 0;
+    return SPCBPT_OK;
+}
+
+// Flipping the switch restarts the accumulation like spcbpt_viewer_set_reproject: the moments of the film have to start with it.
+int spcbpt_viewer_set_denoise(spcbpt_viewer* v, int on) {
+    if (!v) return SPCBPT_ERR_INVALID_ARG;
+    if ((on != 0) == v->denoise) return SPCBPT_OK;
+    if (on && !v->reproject) return SPCBPT_ERR_STATE;   // it filters the resolved image: spcbpt_viewer_set_reproject(v, 1) first
+    if (v->ctx) {
+        int rc = SPCBPT_OK;
+        if (on) {
+            rc = spcbpt_get_film_moments(v->ctx, &v->ctx_moments_before_denoise);
+            if (!rc) rc = spcbpt_set_film_moments(v->ctx, 1);
+        } else {
+            rc = spcbpt_set_film_moments(v->ctx, v->ctx_moments_before_denoise);
+        }
+        if (rc) return rc;
+        if (v->history_held) {   // a history without (or with) a variance does not serve the other form
+            rc = spcbpt_history_reset(v->ctx);
+            if (rc) return rc;
+        }
+    }
+    v->denoise = on != 0;
+    v->reproject_restart = true;
+    v->reproject_live = v->history_held = false;
+    return SPCBPT_OK;
+}
+int spcbpt_viewer_get_denoise(spcbpt_viewer* v, int* on) {
+    if (!v || !on) return SPCBPT_ERR_INVALID_ARG;
+    *on = v->denoise ? 1 : 0;
     return SPCBPT_OK;
 }
 
@@ -441,6 +478,11 @@ int spcbpt_viewer_frame(spcbpt_viewer* v) {
             rc = spcbpt_history_resolve(v->ctx, v->subframe_index + 1);
             if (rc) return rc;
             v->history_held = true;
+            if (v->denoise) {
+                const spcbpt_denoise_params defaults = {5, 0.0f, 0.0f, 0.0f};
+                rc = spcbpt_history_denoise(v->ctx, &defaults);
+                if (rc) return rc;
+            }
         }
         // ---- ahead of the display
         // Mode 2 speculates only from a steady view: a call that itself saw an event (a drag in progress, a resize, a key) is likely to

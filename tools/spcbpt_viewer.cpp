@@ -2,8 +2,9 @@
 // (680-837) with GLFW's event queue replaced by an event script and GLDisplay by PPM snapshots.  Pure C++ over the C ABI:
 // load scene -> create -> initCameraState -> preprocessing (or a checkpoint) -> loop { events; spcbpt_viewer_frame }.
 //   spcbpt_viewer <file.scene | file.gltf | file.glb> <data_root> [--dim=WxH] [--script file | -] [--train-paths N] [--minimal]
-//                 [--load-checkpoint dir] [--save-checkpoint dir] [--reproject]
+//                 [--load-checkpoint dir] [--save-checkpoint dir] [--reproject [--denoise]]
 // --reproject switches the viewer's history reprojection on: `save` then writes the resolved frame (spcbpt_read_history).
+// --denoise (only with --reproject) switches the viewer's denoiser on as well: `save` then writes the denoised frame (spcbpt_read_denoised).
 // Script (one event per line, `#` comments; what a GLFW front end would forward to the same spcbpt_viewer_* calls):
 //   press left|right|middle X Y     release left|right|middle X Y     move X Y     scroll DY     resize W H     iconify 0|1
 //   key ESCAPE|SPACE|C|P|W [press|repeat|release]     fps F (fixed playback rate; 0 = measured)
@@ -36,11 +37,11 @@ static int key_code(const std::string& s) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root> [--dim=WxH] [--script file|-] [--train-paths N] [--minimal] [--load-checkpoint dir] [--save-checkpoint dir] [--reproject]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root> [--dim=WxH] [--script file|-] [--train-paths N] [--minimal] [--load-checkpoint dir] [--save-checkpoint dir] [--reproject [--denoise]]\n", argv[0]);
         return 0;
     }
     int width = 1920, height = 1000, train_paths = 2000000;  // optixPathTracer.cpp:686-687
-    bool minimal = false, reproject = false;
+    bool minimal = false, reproject = false, denoise = false;
     std::string script = "-", load_ckpt, save_ckpt;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
@@ -49,10 +50,12 @@ int main(int argc, char** argv) {
         else if (a == "--train-paths" && i + 1 < argc) train_paths = atoi(argv[++i]);
         else if (a == "--minimal") minimal = true;
         else if (a == "--reproject") reproject = true;
+        else if (a == "--denoise") denoise = true;
         else if (a == "--load-checkpoint" && i + 1 < argc) load_ckpt = argv[++i];
         else if (a == "--save-checkpoint" && i + 1 < argc) save_ckpt = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
+    if (denoise && !reproject) { fprintf(stderr, "--denoise needs --reproject (it filters the resolved image)\n"); return 1; }
     spcbpt_scene_file* sf = nullptr;
     const std::string in(argv[1]);
     const bool gltf = in.size() > 5 && (in.compare(in.size() - 5, 5, ".gltf") == 0 || in.compare(in.size() - 4, 4, ".glb") == 0);
@@ -84,6 +87,7 @@ int main(int argc, char** argv) {
         if (!save_ckpt.empty()) CHECK(ctx, spcbpt_checkpoint_save(ctx, save_ckpt.c_str()));
     }
     if (reproject) CHECK(ctx, spcbpt_viewer_set_reproject(v, 1));
+    if (denoise) CHECK(ctx, spcbpt_viewer_set_denoise(v, 1));
     std::ifstream file;
     if (script != "-") { file.open(script); if (!file) { fprintf(stderr, "cannot open script %s\n", script.c_str()); return 1; } }
     std::istream& src = script == "-" ? std::cin : file;
@@ -124,7 +128,8 @@ int main(int argc, char** argv) {
             ls >> a;
             spcbpt_viewer_get_state(v, &st);
             std::vector<uint8_t> frame((size_t)st.width * st.height * 4);
-            if (reproject) CHECK(ctx, spcbpt_read_history(ctx, nullptr, frame.data(), nullptr, nullptr));
+            if (denoise) CHECK(ctx, spcbpt_read_denoised(ctx, nullptr, frame.data()));
+            else if (reproject) CHECK(ctx, spcbpt_read_history(ctx, nullptr, frame.data(), nullptr, nullptr));
             else CHECK(ctx, spcbpt_read_frame(ctx, frame.data()));
             FILE* f = fopen((a + ".ppm").c_str(), "wb");
             if (!f) { fprintf(stderr, "cannot write %s.ppm\n", a.c_str()); return 1; }
