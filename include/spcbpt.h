@@ -300,10 +300,36 @@ int spcbpt_set_light_trace(spcbpt_ctx* ctx, const spcbpt_light_trace_params* p);
  * and the row arguments select 8-row bands as above (a splat that lands outside them is discarded, so ranks with disjoint band
  * sets render a correctly sharded film from the same cache).  The image converges to what "pt" converges to.  Not with an
  * environment map (SPCBPT_ERR_STATE: the directly seen sky is not sampled by this estimator, and sky vertices have no position),
- * not in the deferred / batched launch forms.  The sum uses float atomics: films agree to rounding, not bit for bit, between runs.
+ * not in the deferred / batched launch forms.  In the default (atomic) mode the sum uses float atomics: films agree to rounding,
+ * not bit for bit, between runs; spcbpt_set_splat_order below selects a sum in a fixed order instead.
  * Event counters are left untouched; the kernel-time span is "lt". */
 int spcbpt_launch(spcbpt_ctx* ctx, const char* name, uint32_t frame,
                   int row_begin, int row_end, int row_step);
+
+/* How "lt" sums the contributions of a pixel (no reference counterpart).  SPCBPT_SPLAT_ATOMIC, the default: three float atomics per
+ * contribution, in order of arrival.  SPCBPT_SPLAT_ORDERED: a launch reads n = min(vertex_count, capacity) vertices of the cache;
+ * vertex i yields at most one record (pixel_i, rgb_i) -- exactly when the atomic mode would have added it, with the same bits -- and
+ * the launch's radiance at pixel p is, per channel, +0.0f plus rgb_i of every record with pixel_i == p in ASCENDING i, one float32
+ * addition per record.  A pixel without a record is +0.0f.  From there the launch goes on as in the atomic mode (running mean by
+ * subframe, moments, tone map).  The film is then the same bits on every run, on every band split and in every context that holds
+ * the same cache.  Costs, per render stream in use: 32 B per vertex of the cache capacity plus a radix sort's temporary storage,
+ * allocated at the first ordered launch, grow-only, released by switching back to the atomic mode and by spcbpt_destroy; a context
+ * that never asks keeps its footprint and its launches.  Any other mode value: SPCBPT_ERR_INVALID_ARG; a deferred frame
+ * outstanding: SPCBPT_ERR_STATE.  Switching back waits for the context's streams.  Every refusal of "lt" holds in both modes. */
+enum { SPCBPT_SPLAT_ATOMIC = 0, SPCBPT_SPLAT_ORDERED = 1 };
+int spcbpt_set_splat_order(spcbpt_ctx* ctx, int mode);
+int spcbpt_get_splat_order(spcbpt_ctx* ctx, int* mode);
+/* The records of the last ordered "lt" launch, in cache order: *count = n, and for i < n pixel[i] = y * width + x with rgb[3 i ..]
+ * the contribution, or pixel[i] = -1 (rgb 0) where vertex i yields no record (culled, occluded, outside the launch's rows).  What
+ * a caller needs who wants a reconstruction filter of their own.  Waits like spcbpt_read_accum.  SPCBPT_ERR_STATE if there has been
+ * no ordered launch since the last spcbpt_resize (or since the mode went back to atomic); SPCBPT_ERR_CAPACITY if `capacity`
+ * (records the arrays hold) is below n -- *count is still set, nothing else is written. */
+int spcbpt_read_splat_records(spcbpt_ctx* ctx, float* rgb, int32_t* pixel, int capacity, int* count);
+/* The ordered sum over caller arrays on the host: n records (rgb 3 floats each, pixel index), out_rgb 3 floats per pixel of a
+ * width x height film; records whose pixel is negative or >= width * height are skipped.  The code k_lt_gather runs (float32, no
+ * contraction); no context and no GPU needed.  SPCBPT_ERR_INVALID_ARG for a NULL pointer (rgb / pixel may be NULL when n == 0),
+ * n < 0 or an empty film. */
+int spcbpt_splat_sum_host(const float* rgb, const int32_t* pixel, int64_t n, int width, int height, float* out_rgb);
 
 /* The camera as the end of a light sub-path: where `point` lands on a width x height film seen through (eye, U, V, W) -- any
  * frame spcbpt_set_camera accepts, orthogonal or not -- and the importance "lt" gives it.  With c = point - eye, D = U . (V x W):

@@ -478,6 +478,24 @@ def history_denoise_host(resolved, resolved_var, albedo, normal_depth, eye, U, V
     return out
 
 
+SPLAT_ATOMIC, SPLAT_ORDERED = 0, 1   # spcbpt_set_splat_order
+
+
+def splat_sum_host(rgb, pixel, width, height):
+    """spcbpt_splat_sum_host: the ordered splat sum of "lt" on the host -- (height, width, 3) float32, every pixel +0.0 plus the rgb of
+    its records in ascending record index, one float32 addition each; records with a pixel index < 0 or >= width * height are skipped."""
+    lib = load_library()
+    c = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    p = np.ascontiguousarray(pixel, np.int32).reshape(-1)
+    if len(c) != len(p):
+        raise SpcbptError("splat_sum_host: rgb must hold three floats per entry of pixel")
+    out = np.empty((int(height), int(width), 3), np.float32)
+    rc = lib.spcbpt_splat_sum_host(_fp(c) if len(p) else None, p.ctypes.data_as(C.POINTER(C.c_int32)) if len(p) else None, len(p), int(width), int(height), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"splat_sum_host failed ({rc})")
+    return out
+
+
 def film_moments_update_host(mean_before, sample, subframe, m2n):
     """spcbpt_film_moments_update_host: one merge's update of the moment plane `m2n` ((..., 4) float32, C-contiguous, updated IN PLACE)
     from the film before the merge and the frame's samples (same shape).  The per-pixel function the kernel runs; no GPU needed."""
@@ -790,6 +808,10 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_trace_closest": [vp, vp, i32, vp, vp, vp],
         "spcbpt_trace_any": [vp, vp, i32, vp],
         "spcbpt_camera_splat": [f32p, f32p, f32p, f32p, i32, i32, f32p, f32p, f32p, C.POINTER(i32), C.POINTER(i32), f32p],
+        "spcbpt_set_splat_order": [vp, i32],
+        "spcbpt_get_splat_order": [vp, C.POINTER(i32)],
+        "spcbpt_read_splat_records": [vp, f32p, C.POINTER(C.c_int32), i32, C.POINTER(i32)],
+        "spcbpt_splat_sum_host": [f32p, C.POINTER(C.c_int32), C.c_int64, i32, i32, f32p],
         "spcbpt_launch_features": [vp, u32, i32, i32, i32],
         "spcbpt_read_features": [vp, vp, vp],
         "spcbpt_denoise": [vp, C.POINTER(DenoiseParams)],
@@ -876,6 +898,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench",
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
+    "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
@@ -978,9 +1001,35 @@ class Renderer:
     # -- launches -----------------------------------------------------------
     def launch(self, name: str, frame: int, rows=None):
         """spcbpt_launch: "light trace", "pt", "SPCBPT_eye", "SPCBPT_no_rmis", "pretrace", or "lt" -- light tracing, the light-vertex
-        cache of the last built sampler splatted onto the film (no environment map; float atomics, so not bit-reproducible)."""
+        cache of the last built sampler splatted onto the film (no environment map; float atomics, so not bit-reproducible, unless
+        set_splat_order(SPLAT_ORDERED) has been called)."""
         r0, r1, rs = rows if rows is not None else (0, self.height, 1)
         self._chk(self.lib.spcbpt_launch(self.h, name.encode(), frame, r0, r1, rs), f"launch({name})")
+
+    def set_splat_order(self, mode):
+        """spcbpt_set_splat_order: SPLAT_ATOMIC (0, the default) or SPLAT_ORDERED (1): "lt" sums every pixel's contributions in
+        ascending cache order, so its film is the same bits on every run (32 B per cache vertex and render stream, a radix sort per
+        launch).  True / False select ordered / atomic."""
+        self._chk(self.lib.spcbpt_set_splat_order(self.h, int(mode)), "set_splat_order")
+
+    def splat_order(self) -> int:
+        v = C.c_int32()
+        self._chk(self.lib.spcbpt_get_splat_order(self.h, C.byref(v)), "get_splat_order")
+        return v.value
+
+    def read_splat_records(self, capacity=None):
+        """spcbpt_read_splat_records: (rgb (n, 3) float32, pixel (n,) int32) of the last ordered "lt" launch, one entry per vertex
+        of the cache it read, in cache order; pixel = y * width + x, or -1 where the vertex added nothing."""
+        n = C.c_int()
+        if capacity is None:   # ask for the count first (no buffers: SPCBPT_ERR_CAPACITY with the count set, unless it is 0)
+            rc = self.lib.spcbpt_read_splat_records(self.h, None, None, 0, C.byref(n))
+            if rc not in (0, -6):
+                self._chk(rc, "read_splat_records")
+            capacity = n.value
+        rgb = np.zeros((max(capacity, 1), 3), np.float32)
+        pixel = np.full(max(capacity, 1), -1, np.int32)
+        self._chk(self.lib.spcbpt_read_splat_records(self.h, _fp(rgb), pixel.ctypes.data_as(C.POINTER(C.c_int32)), int(capacity), C.byref(n)), "read_splat_records")
+        return rgb[:n.value].copy(), pixel[:n.value].copy()
 
     def launch_features(self, subframe: int, rows=None):
         """spcbpt_launch_features: the first hit of the film's primary ray of `subframe` (albedo + coverage, geometric normal + depth)

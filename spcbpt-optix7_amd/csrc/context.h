@@ -315,6 +315,24 @@ struct Context {
     // atomics) per render stream, allocated at the first "lt" launch of that stream after a resize.
     DevBuf<float> d_splat[kMaxRender];
     int launch_splat(uint32_t frame, int r0, int r1, int rs);
+    // The ordered mode of "lt" (spcbpt_set_splat_order, off by default): every vertex's contribution stored in the vertex's own slot,
+    // a stable radix sort of (pixel, slot) and a per-pixel sum in slot order -- no atomics, the same film bits on every run.  Per render
+    // stream and cache slot 32 B (a float4 record, the sort's key and value double buffers) plus hipcub's temporary storage and 4 B for
+    // the launch's vertex count; allocated at the first ordered launch of the stream, grow-only with the cache capacity, released when
+    // the mode goes back to atomic and at destroy: a context that never asks keeps its footprint, its launches and its film bits.
+    struct SplatOrdered {
+        DevBuf<float> records;                        // float4 per slot: (rgb, bits of the pixel index or of the pad key)
+        DevBuf<uint32_t> keys, vals, keys2, vals2;    // the sort's input (written by k_lt_records) and output
+        DevBuf<unsigned char> temp;
+        DevBuf<int> count;                            // sampler_counts[0] of the set the last launch read, copied behind that launch
+        void release() { records.release(); keys.release(); vals.release(); keys2.release(); vals2.release(); temp.release(); count.release(); }
+    } d_ordered[kMaxRender];
+    int splat_order = 0;              // SPCBPT_SPLAT_ATOMIC / SPCBPT_SPLAT_ORDERED
+    int splat_records_rk = -1;        // the render stream whose buffers hold the last ordered launch's records (-1: none since the last resize)
+    int splat_records_capacity = 0, splat_records_pixels = 0;   // ... the cache capacity and the pad key of that launch
+    int set_splat_order(int mode);
+    int splat_bound(int capacity);    // a host-known upper bound of set eset's vertex count, found without a host wait
+    int read_splat_records(float* rgb, int32_t* pixel, int capacity, int* count);
     // Prologue and epilogue of the launches that end in a film merge (ctx_render.hip)
     int film_ready();                          // no deferred frame outstanding, a film, a camera
     int begin_render(int r0, int r1, int rs);  // the band of rows into kp, then the next render stream

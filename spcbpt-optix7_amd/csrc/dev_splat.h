@@ -8,7 +8,7 @@
 
 namespace spc {
 
-struct SplatParams {  // passed by value as the kernel argument block of k_lt_splat / k_lt_resolve
+struct SplatParams {  // passed by value as the kernel argument block of the kernels of kernels_splat.hip
     DeviceScene scene;
     float eye[3], U[3], V[3], W[3];
     uint32_t width, height, subframe;
@@ -21,6 +21,14 @@ struct SplatParams {  // passed by value as the kernel argument block of k_lt_sp
     uint32_t* spill;                       // per-thread traversal stack overflow area
     int32_t spill_entries;
     uint32_t* diag;
+    // the ordered mode (spcbpt_set_splat_order; null / 0 in the atomic mode): k_lt_records fills slot i of `records`, `keys` and
+    // `vals` for every i in [0, bound); a stable sort of (keys, vals) over `bound` items leaves keys_sorted / vals_sorted for k_lt_gather
+    float4* records;                       // per cache slot: (rgb, the bits of the pixel index or of the pad key width * height)
+    uint32_t* keys;                        // per cache slot: the pixel index, or the pad key
+    uint32_t* vals;                        // per cache slot: i
+    const uint32_t* keys_sorted;
+    const uint32_t* vals_sorted;
+    int32_t bound;                         // host-known upper bound of min(sampler_counts[0], capacity), <= capacity
 };
 
 // is row y one of the launch's rows? (lane_pixel / tile_pixel of eye_walk.h enumerate exactly these)
@@ -34,6 +42,7 @@ struct SplatJob {
     float tmax;
     f3 contrib;
     uint32_t pixel;   // y * width + x
+    uint32_t index;   // the vertex's slot in the cache (set by k_lt_records, which has to know where a record goes; splat_cull leaves it)
 };
 
 // One cache vertex against the camera.  False = the vertex contributes nothing whatever the visibility (behind the camera, outside

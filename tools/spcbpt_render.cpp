@@ -4,14 +4,15 @@
 // that names an `env_file` gets its sky (spcbpt_set_environment); --env-mode N sets spcbpt_set_environment_mode (SPCBPT_ENV_* bits).
 // --emissive: the emissive materials of a glTF file light the scene as mesh lights (spcbpt_create_lit); with them a file needs no quad.
 // --alg lt: light tracing (the light-vertex cache splatted onto the film): a light pass and a sampler build per frame over the minimal
-// tuple, no preprocessing; its Mpaths/s line counts the light paths only.
+// tuple, no preprocessing; its Mpaths/s line counts the light paths only.  --ordered-splat: "lt" sums every pixel's contributions in cache
+// order (spcbpt_set_splat_order(ctx, SPCBPT_SPLAT_ORDERED)): two runs write the same bytes.
 // --denoise: a first-hit feature launch beside every frame and one a-trous denoise (spcbpt_denoise, default parameters) after the last;
 // writes <out>_denoised.pfm / .ppm next to the usual files.  --features: writes the feature buffers as <out>_albedo.pfm,
 // <out>_normal.pfm and <out>_depth.pfm (depth in all three channels).
 // --denoise-variance: the same with the variance-guided filter (spcbpt_denoise_variance; switches the film's moments on).
 // --target-error E [--check-every K]: switches the film's moments on and renders until spcbpt_film_error's mean is <= E (asked every K
 // frames, default 8, from the second frame on) or --frames is reached; prints the frames used and the error reached.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <chrono>
 #include <cstdio>
@@ -51,13 +52,13 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
     int env_mode = 0;
-    bool minimal = false, emissive = false, denoise = false, features = false, denoise_variance = false;
+    bool minimal = false, emissive = false, ordered_splat = false, denoise = false, features = false, denoise_variance = false;
     double target_error = 0.0;   // > 0: stop once the film's mean relative standard error is there
     int check_every = 8;
     for (int i = 3; i < argc; i++) {
@@ -69,6 +70,7 @@ int main(int argc, char** argv) {
         else if (a == "--minimal") minimal = true;
         else if (a == "--env-mode" && i + 1 < argc) env_mode = atoi(argv[++i]);
         else if (a == "--emissive") emissive = true;
+        else if (a == "--ordered-splat") ordered_splat = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-variance") denoise = denoise_variance = true;
         else if (a == "--features") features = true;
@@ -118,6 +120,10 @@ int main(int argc, char** argv) {
     CHECK(ctx, spcbpt_set_environment_mode(ctx, env_mode));
     CHECK(ctx, spcbpt_set_camera_lookat(ctx, eye, lookat, up, fov, (float)width / (float)height));
     CHECK(ctx, spcbpt_resize(ctx, width, height));
+    if (ordered_splat) {
+        CHECK(ctx, spcbpt_set_splat_order(ctx, SPCBPT_SPLAT_ORDERED));
+        printf("splat order: ordered (the film of \"lt\" is bit-reproducible)\n");
+    }
     const bool moments = denoise_variance || target_error > 0.0;
     if (moments) CHECK(ctx, spcbpt_set_film_moments(ctx, 1));
     if (check_every < 1) check_every = 1;
