@@ -29,6 +29,7 @@ __device__ __attribute__((noinline)) static uint32_t stack_pop_slow(const uint32
     if (spill && idx < spill_entries) return spill[idx];
     return NODE_EMPTY;  // the entry push() had to drop (and counted in diag[0]): a leaf of zero triangles, nothing is read
 }
+static constexpr int kTravDone = 0x7fffffff;   // the traversal state `node` of a lane that holds no ray (any more); as a stack word it decodes as itself (bit 31 clear)
 template <int BLOCK, int STACK_LDS>
 struct TravStack {
     lds_u32* wave_lds;  // column 0 of this wave inside the BLOCK * STACK_LDS dword array (wave-uniform)
@@ -82,6 +83,33 @@ struct TravStack {
         sp = p1 + (c1 ? 1 : 0);
     }
     SPC_DEV uint32_t pop_lds() { sp--; return column()[sp * BLOCK]; }
+    // ---- the same two without control flow (the LDS-only node step of trace_pool): exec-mask bookkeeping around regions of
+    // one or two instructions was over a third of that loop (profiles/r09_experiments.md) ----
+    // Where the accesses go.  The caller runs these only for lanes that hold a ray (node != kTravDone) in an iteration whose vote
+    // established sp + 3 <= STACK_LDS for exactly those lanes; a lane whose ray ended keeps a stale sp and is masked off there.  With
+    // 0 <= sp <= STACK_LDS - 3: top_lds() reads entry max(sp - 1, 0) in 0 .. STACK_LDS - 4, next_flat() writes entries sp, sp + c3 and
+    // sp + c3 + c2, all in sp .. sp + 2 <= STACK_LDS - 1 -- every access is in the lane's own column, no index is formed from a
+    // value read back, and what lies at or above the new sp is never read before it is written again: a traversal is the same
+    // finite sequence of words as with push_far_lds / pop_lds.
+    // The entry a pop would return, read before the step knows whether it pops (the slab arithmetic covers the round trip); with an
+    // empty stack entry 0, which next_flat() does not use.
+    SPC_DEV uint32_t top_lds() const { return column()[(sp > 0 ? sp - 1 : 0) * BLOCK]; }
+    // One visit's stack traffic: the three farther children stored unconditionally at computed slots, farthest first (c1 >= c2 >= c3;
+    // a child that missed is overwritten by the next store to the same slot or is left above the new sp -- a lane's DS operations retire
+    // in order), and the word the lane continues with: the nearest child r0, or after a miss of all four (`miss`, then c1 = c2 = c3 =
+    // false) the popped entry `top`, or kTravDone from an empty stack.  (Fixed slots sp, sp + 1, sp + 2 with the selects on the words
+    // instead of the addresses came out 18 instructions longer in the loop: profiles/r09_experiments.md.)
+    SPC_DEV uint32_t next_flat(uint32_t top, bool miss, uint32_t r0, uint32_t r1, bool c1, uint32_t r2, bool c2, uint32_t r3, bool c3) {
+        lds_u32* lds = column();
+        lds[sp * BLOCK] = r3;
+        const int p2 = sp + (c3 ? 1 : 0);
+        lds[p2 * BLOCK] = r2;
+        const int p1 = p2 + (c2 ? 1 : 0);
+        lds[p1 * BLOCK] = r1;
+        const uint32_t popped = sp == 0 ? (uint32_t)kTravDone : top;
+        sp = miss ? (sp > 0 ? sp - 1 : 0) : p1 + (c1 ? 1 : 0);
+        return miss ? popped : r0;
+    }
 };
 
 struct HitRec { float t; int tri; float u, v; };
@@ -131,7 +159,6 @@ SPC_DEV bool tri_test(float4 q0, float4 q1, float4 q2, f3 o, f3 d, float tmin, f
 // ANY = terminate on first hit, no culling (visibilityTest); else nearest hit with emitter back-face culling.
 // "while-while" traversal: all lanes first descend through internal nodes (lanes that already sit on a leaf wait), then
 // the wave processes leaves together, so the two code paths are not interleaved per iteration inside a divergent wave.
-static constexpr int kTravDone = 0x7fffffff;
 #ifndef SPC_TRI_BATCH
 #define SPC_TRI_BATCH 8   // trace_pool: N > 1 = lanes on a leaf wait until N of them are (or nobody is on an internal node) before the triangle step
 #endif
@@ -141,6 +168,13 @@ static constexpr int kTravDone = 0x7fffffff;
     do {                                                                                                              \
         if ((W) & 0x80000000u) { NODE = ~(int)(((W) & 0x7fffffffu) >> 3); LEAF = (int)((W) & 7u); }                   \
         else NODE = (int)(W);                                                                                         \
+    } while (0)
+// ... by selects (a word without bit 31 leaves LEAF as it is, as above)
+#define SPC_STACK_DECODE_SEL(W, NODE, LEAF)                                                                           \
+    do {                                                                                                              \
+        const bool lf__ = ((W) & 0x80000000u) != 0u;                                                                  \
+        NODE = lf__ ? ~(int)(((W) & 0x7fffffffu) >> 3) : (int)(W);                                                    \
+        LEAF = lf__ ? (int)((W) & 7u) : LEAF;                                                                         \
     } while (0)
 // pop the next stack entry into (node, leaf_count)
 #define SPC_TRAV_POP() SPC_TRAV_POP_(pop)
@@ -220,11 +254,6 @@ SPC_DEV QuadSlab slab1q_impl(const float4 rec, f3 inv, f3 ood, float tmin, float
 }
 SPC_DEV QuadSlab slab1q(const float4 rec, f3 inv, f3 ood, float tmin, float tmax, uint32_t qr) { return slab1q_impl<true>(rec, inv, ood, tmin, tmax, qr); }
 SPC_DEV uint32_t slab1q_key(const float4 rec, f3 inv, f3 ood, float tmin, float tmax, uint32_t qr) { return slab1q_impl<false>(rec, inv, ood, tmin, tmax, qr).key; }
-SPC_DEV uint32_t sel4u(const uint32_t r[4], uint32_t i) {  // two-level select: three v_cndmask, no control flow
-    const uint32_t a = (i & 1u) ? r[1] : r[0];
-    const uint32_t b = (i & 1u) ? r[3] : r[2];
-    return (i & 2u) ? b : a;
-}
 SPC_DEV uint32_t stack_word(int ref, int count) {
     return ref >= 0 ? (uint32_t)ref : (0x80000000u | ((uint32_t)(~ref) << 3) | (uint32_t)count);
 }
@@ -246,14 +275,14 @@ SPC_DEV uint32_t stack_word(int ref, int count) {
     do {                                                                                                              \
         cn.add(C_NODE); /* one 64-B visit */                                                                          \
         SPC_UTIL_COUNT(C_U_NODE_LANES, C_U_NODE_SLOTS)                                                                \
-        const uint32_t ref__[4] = {__float_as_uint(Q2.z), __float_as_uint(Q2.w), __float_as_uint(Q3.x),               \
-                                   __float_as_uint(Q3.y)};                                                            \
+        uint32_t ref__[4] = {__float_as_uint(Q2.z), __float_as_uint(Q2.w), __float_as_uint(Q3.x),                     \
+                             __float_as_uint(Q3.y)};                                                                  \
         uint32_t k__[4];                                                                                              \
         slab4q(Q0, Q1, Q2, ood, inv, TMIN, TMAX, k__);                                                                \
-        /* sort the four keys ascending: nearest child first (5 compare-exchanges); misses (0xffffffff) end up last */ \
+        /* sort the four keys ascending: nearest child first (5 compare-exchanges); misses (0xffffffff) end up last.  The child */ \
+        /* words travel with their keys (two selects per exchange; picking them afterwards by the keys' slot bits was 28 instructions) */ \
         SPC_CSWAP__(0, 1) SPC_CSWAP__(2, 3) SPC_CSWAP__(0, 2) SPC_CSWAP__(1, 3) SPC_CSWAP__(1, 2)                      \
-        const uint32_t r0__ = sel4u(ref__, k__[0] & 3u), r1__ = sel4u(ref__, k__[1] & 3u),                            \
-                       r2__ = sel4u(ref__, k__[2] & 3u), r3__ = sel4u(ref__, k__[3] & 3u);                            \
+        const uint32_t r0__ = ref__[0], r1__ = ref__[1], r2__ = ref__[2], r3__ = ref__[3];                            \
         if (k__[0] == 0xffffffffu) {                                                                                  \
             SPC_TRAV_POP_(POP);                                                                                       \
         } else {                                                                                                      \
@@ -261,7 +290,25 @@ SPC_DEV uint32_t stack_word(int ref, int count) {
             SPC_STACK_DECODE(r0__, node, leaf_count);                                                                 \
         }                                                                                                             \
     } while (0)
-#define SPC_CSWAP__(a, b) { const uint32_t lo__ = min(k__[a], k__[b]), hi__ = max(k__[a], k__[b]); k__[a] = lo__; k__[b] = hi__; }
+// ... straight-line, on the LDS part of the stack alone (TravStack::next_flat; TOP is st.top_lds() of the step's start): no `if` after
+// the slab test.  The same keys, the same order, the same words on the stack below sp and the same (node, leaf_count, sp) afterwards as
+// SPC_NODE_STEP_Q with push_far_lds / pop_lds (tests/native/stack_step_check.cpp holds the two transitions against each other).
+#define SPC_NODE_STEP_FLAT_Q(TMIN, TMAX, Q0, Q1, Q2, Q3, TOP)                                                         \
+    do {                                                                                                              \
+        cn.add(C_NODE); /* one 64-B visit */                                                                          \
+        SPC_UTIL_COUNT(C_U_NODE_LANES, C_U_NODE_SLOTS)                                                                \
+        uint32_t ref__[4] = {__float_as_uint(Q2.z), __float_as_uint(Q2.w), __float_as_uint(Q3.x),                     \
+                             __float_as_uint(Q3.y)};                                                                  \
+        uint32_t k__[4];                                                                                              \
+        slab4q(Q0, Q1, Q2, ood, inv, TMIN, TMAX, k__);                                                                \
+        SPC_CSWAP__(0, 1) SPC_CSWAP__(2, 3) SPC_CSWAP__(0, 2) SPC_CSWAP__(1, 3) SPC_CSWAP__(1, 2)                      \
+        const uint32_t r0__ = ref__[0], r1__ = ref__[1], r2__ = ref__[2], r3__ = ref__[3];                            \
+        const uint32_t w__ = st.next_flat(TOP, k__[0] == 0xffffffffu, r0__, r1__, k__[1] != 0xffffffffu,              \
+                                          r2__, k__[2] != 0xffffffffu, r3__, k__[3] != 0xffffffffu);                  \
+        SPC_STACK_DECODE_SEL(w__, node, leaf_count);                                                                  \
+    } while (0)
+#define SPC_CSWAP__(a, b) { const bool sw__ = k__[b] < k__[a]; const uint32_t lo__ = min(k__[a], k__[b]), hi__ = max(k__[a], k__[b]); k__[a] = lo__; k__[b] = hi__; \
+                            const uint32_t ra__ = sw__ ? ref__[b] : ref__[a], rb__ = sw__ ? ref__[a] : ref__[b]; ref__[a] = ra__; ref__[b] = rb__; }
 
 // ANY = terminate on first hit, no culling (visibilityTest); else nearest hit with emitter back-face culling.
 // Schedule: "if-if" -- every iteration of the wave does one node visit for the lanes that sit on an internal node and then
@@ -620,15 +667,17 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
             asm volatile("" : "+v"(R2.x), "+v"(R2.y), "+v"(R2.z), "+v"(R2.w), "+v"(R3.x), "+v"(R3.y), "+v"(R3.z), "+v"(R3.w));
             // The step, in two instantiations: with the plain stack operations (bounds logic and call sites of the HBM part at every push and
             // pop: ~30 instructions that a step pays whether or not any lane is near the end of its 16 LDS entries), and with the LDS-only
-            // ones for the iterations in which no lane of the wave is (a vote per iteration; probe: 1.8 % of the kernel).
-#define SPC_POOL_STEP__(PUSH, POP)                                                                                    \
+            // ones for the iterations in which no lane of the wave is (a vote per iteration; probe: 1.8 % of the kernel).  The node step
+            // of the LDS-only one is the straight-line form; every lane with a ray asks for the top of its stack ahead of the branches
+            // (PRE; inside the node step's arm the read compiles to the same loop: profiles/r09_experiments.md).
+#define SPC_POOL_STEP__(PRE, NODE_STEP, POP)                                                                          \
             do {                                                                                                      \
+                PRE;                                                                                                  \
                 const bool at_leaf = node < 0;                                                                        \
-                if (!at_leaf) { SPC_NODE_STEP_Q(kEps, best_t, R0, R1, R2, R3, PUSH, POP); finished = node == kTravDone; } \
+                if (!at_leaf) { NODE_STEP; }                                                                          \
                 else if (hold__) { /* SPC_TRI_BATCH: the triangle step waits for company (its record stays in R0..R3) */ } \
                 else if (leaf_count <= 0) {                                                                           \
                     SPC_TRAV_POP_(POP);  /* an empty slot's zero-triangle leaf (only reachable through rounding): nothing to test */ \
-                    finished = node == kTravDone;                                                                     \
                 } else {                                                                                              \
                     const int tri = ~node;                                                                            \
                     cn.add(C_TRI);                                                                                    \
@@ -649,17 +698,18 @@ SPC_DEV void trace_pool(const DeviceScene& S, TravStack<BLOCK, STACK_LDS>& st, b
                         h = h || hb__;                                                                                \
                     }                                                                                                 \
                     if (h && !closest) {                                                                              \
-                        occluded = true; finished = true; node = kTravDone;                                           \
+                        occluded = true; node = kTravDone;                                                            \
                     } else {                                                                                          \
                         const int adv__ = pair__ ? 2 : 1;                                                             \
                         node -= adv__;  /* ~(tri + 1) */                                                              \
                         leaf_count -= adv__;                                                                          \
-                        if (leaf_count == 0) { SPC_TRAV_POP_(POP); finished = node == kTravDone; }                    \
+                        if (leaf_count == 0) SPC_TRAV_POP_(POP);                                                      \
                     }                                                                                                 \
                 }                                                                                                     \
+                finished = node == kTravDone;  /* one test for every way a ray ends: a pop from an empty stack, an occluder */ \
             } while (0)
-            if (shallow__) SPC_POOL_STEP__(push_far_lds, pop_lds);
-            else SPC_POOL_STEP__(push_far, pop);
+            if (shallow__) SPC_POOL_STEP__(const uint32_t top__ = st.top_lds(), SPC_NODE_STEP_FLAT_Q(kEps, best_t, R0, R1, R2, R3, top__), pop_lds);
+            else SPC_POOL_STEP__((void)0, SPC_NODE_STEP_Q(kEps, best_t, R0, R1, R2, R3, push_far, pop), pop);
 #undef SPC_POOL_STEP__
         }
         if ((node != kTravDone || !done) && !hold__) SPC_FETCH_STEP__();   // the next step's record: ONE request site after the step, outside its branches
