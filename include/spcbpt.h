@@ -545,6 +545,63 @@ int spcbpt_film_error(spcbpt_ctx* ctx, spcbpt_film_error_stats* out);
 /* The same over caller arrays on the host (float4 per pixel each), pixels in index order.  SPCBPT_ERR_INVALID_ARG as above. */
 int spcbpt_film_error_host(const float* accum_rgba, const float* m2n, int64_t n_pixels, spcbpt_film_error_stats* out);
 
+/* Adaptive sampling (no reference counterpart), opt-in: trace only the tiles of the film that are still above a target error.  A TILE
+ * is an 8x8 pixel block of the whole film, numbered x-major: tile t covers x = (t % tiles_x) 8 ..., y = (t / tiles_x) 8 ... with
+ * tiles_x = ceil(width / 8); edge tiles are partial.  The adaptive state of a context is a sample count per tile (uint32), an error
+ * per tile (float) and a tile list (uint32, strictly ascending) with its length.
+ *
+ * spcbpt_adaptive_begin(ctx, frames) declares that the film holds the uniform subframes 0 .. frames - 1 (spcbpt_history_capture's
+ * convention) and sets every tile's count to `frames` (0 is allowed); the list starts empty.  It needs the film's moments switched
+ * on and no deferred frame outstanding (else SPCBPT_ERR_STATE), and waits for the context's streams.  While the mode is active every
+ * call that merges into the film with one weight for all pixels -- spcbpt_launch of "pt", "SPCBPT_eye", "SPCBPT_no_rmis" and "lt",
+ * spcbpt_launch_deferred, spcbpt_launch_eye_batch -- and spcbpt_set_film_moments(ctx, 0) return SPCBPT_ERR_STATE with a text that
+ * names adaptive sampling; "light trace", "pretrace", the sampler builds, spcbpt_launch_features, the denoisers, the history calls,
+ * spcbpt_film_error and every read work as before (they only read the film, and the moments plane carries each pixel's own n).
+ * spcbpt_adaptive_end, spcbpt_resize and spcbpt_clear_accum end the mode and drop the counts; spcbpt_adaptive_end leaves the film as it is.
+ *
+ * spcbpt_adaptive_select computes, for every tile, e_t = the mean of e(p) (spcbpt_film_error's per-pixel term) over the tile's
+ * pixels inside the image that have n >= 2 -- none: e_t = 0 and the tile is "unknown" -- and lists tile t, in ascending order, iff
+ *   (max_samples == 0 || samples_t < max_samples)  &&  (samples_t < max(min_samples, 2) || t is unknown || e_t > target_error).
+ * Float32; the 64 slot terms of a tile are added by halving (slot s + 32 to slot s, then + 16, ... + 1): one wave per tile, a fixed
+ * shuffle tree, and one block that scans the tiles -- no atomics, so the same film gives the same bits.  The call waits for the merges
+ * queued so far and for its own result, and returns the list's length in *n_selected (may be NULL).  The kernel-time span is
+ * "adaptive_select".  A stopping rule that reads an estimate computed from the samples it stops biases the result slightly towards
+ * early stops; min_samples is the guard.  Beyond that rule every sample is exactly the uniform renderer's.
+ *
+ * spcbpt_adaptive_set_tiles imposes a list instead (region rendering, tests): strictly ascending and in range, else
+ * SPCBPT_ERR_INVALID_ARG; n = 0 is allowed.  It waits for the context's streams.
+ *
+ * spcbpt_launch_adaptive(ctx, "SPCBPT_eye") has the preconditions of spcbpt_launch(ctx, "SPCBPT_eye", ...) -- film, camera, a light
+ * pass, a built sampler -- and traces ONE sample for every pixel of every listed tile: a pixel of tile t uses samples_t wherever an
+ * ordinary launch uses its subframe (seed and jitter of the camera ray, the weight 1 / (samples_t + 1) of the running mean, the
+ * subframe of the moments update: 0 restarts).  It then merges the listed tiles only and adds 1 to their counts.  Pixels of unlisted
+ * tiles keep every bit of accum, frame and the moments plane; an empty list is a successful no-op.  Any other algorithm name:
+ * SPCBPT_ERR_INVALID_ARG.  SPCBPT_ERR_STATE with event counters on, with SPCBPT_ENV_EYE_SEES_SKY set, or with classifier trees
+ * that have direction nodes (the forms the timed kernels do not cover).  Asynchronous; the kernel-time spans are "adaptive_eye" and
+ * "adaptive_merge".
+ *
+ * spcbpt_read_adaptive copies the counts and the errors of the last select ([tiles_y * tiles_x] each) and the list (at most `capacity`
+ * entries; SPCBPT_ERR_INVALID_ARG if it holds more) to the host and leaves the list's length in *n; every pointer is optional.  It
+ * waits like spcbpt_read_accum.  spcbpt_get_adaptive_state never waits (inactive: 0, 0, 0, 0). */
+typedef struct spcbpt_adaptive_params {
+    float target_error;     /* a tile whose mean relative standard error is above this is traced again */
+    uint32_t min_samples;   /* every tile gets at least max(min_samples, 2) samples */
+    uint32_t max_samples;   /* no tile gets more than this; 0 = no cap */
+} spcbpt_adaptive_params;
+int spcbpt_adaptive_params_struct_size(void);   /* sizeof(spcbpt_adaptive_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+int spcbpt_adaptive_begin(spcbpt_ctx* ctx, uint32_t frames);
+int spcbpt_adaptive_end(spcbpt_ctx* ctx);
+int spcbpt_adaptive_select(spcbpt_ctx* ctx, const spcbpt_adaptive_params* params, int* n_selected);
+int spcbpt_adaptive_set_tiles(spcbpt_ctx* ctx, const uint32_t* tiles, int n);
+int spcbpt_launch_adaptive(spcbpt_ctx* ctx, const char* algorithm);
+int spcbpt_read_adaptive(spcbpt_ctx* ctx, uint32_t* tile_samples, float* tile_error, uint32_t* tiles, int capacity, int* n);
+int spcbpt_get_adaptive_state(spcbpt_ctx* ctx, int* active, int* tiles_x, int* tiles_y, int* n_listed);
+/* The selection over caller arrays on the host (float4 per pixel each, tile_samples per tile): the per-tile functions the kernels run,
+ * in their order.  tile_error_out ([tiles]), tiles_out ([tiles] at most) and n_out are optional.  No context and no GPU needed.
+ * SPCBPT_ERR_INVALID_ARG for a NULL input pointer, a size outside 1 .. 2^28 pixels or a target that is not a number. */
+int spcbpt_adaptive_select_host(const float* accum_rgba, const float* m2n, int width, int height, const uint32_t* tile_samples,
+                                const spcbpt_adaptive_params* params, float* tile_error_out, uint32_t* tiles_out, int* n_out);
+
 /* Variance-guided a-trous denoiser: the pipeline, guides, buffers and outputs of spcbpt_denoise (read with spcbpt_read_denoised),
  * with a colour weight measured in the pixel's own standard error instead of a fixed relative width -- so the filter narrows as
  * the film converges and becomes the identity in the limit, where spcbpt_denoise blurs a 4-frame and a 4000-frame film alike.
@@ -870,7 +927,8 @@ int spcbpt_reuse_sampler(spcbpt_ctx* ctx);
 int spcbpt_lvc_import_wait(spcbpt_ctx* ctx);
 
 /* Kernel timing measured with HIP events on the context's stream: average
- * milliseconds per launch of `name` since the last reset, and launch count. */
+ * milliseconds per launch of `name` since the last reset, and launch count.  (The film merge behind a render launch is the span
+ * "film_merge", the moments update in front of it "moments".) */
 int spcbpt_kernel_time(spcbpt_ctx* ctx, const char* name, double* avg_ms, int* launches);
 int spcbpt_reset_kernel_time(spcbpt_ctx* ctx);
 int spcbpt_enable_kernel_timing(spcbpt_ctx* ctx, int enabled);

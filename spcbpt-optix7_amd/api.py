@@ -64,6 +64,10 @@ class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
         return {"pixels": int(self.pixels), "mean": float(self.mean), "max": float(self.max)}
 
 
+class AdaptiveParams(C.Structure):   # spcbpt_adaptive_params
+    _fields_ = [("target_error", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("texcoords", C.c_void_p), ("n_vertices", C.c_int32),
                 ("indices", C.c_void_p), ("tri_material", C.c_void_p), ("n_triangles", C.c_int32),
@@ -525,6 +529,29 @@ def film_error_host(accum, m2n):
     return out.as_dict()
 
 
+def adaptive_select_host(accum, m2n, tile_samples, target_error, min_samples=0, max_samples=0):
+    """spcbpt_adaptive_select_host: the tile errors and the tile list of adaptive sampling from (h, w, 4) float32 arrays as read_accum /
+    read_film_moments give them and the per-tile sample counts ((tiles_y, tiles_x) or flat; tiles are 8x8 pixels, x-major).  Returns
+    {"error": (tiles_y, tiles_x) float32, "tiles": ascending uint32 list}.  The per-tile functions the kernels run; no GPU needed."""
+    lib = load_library()
+    a, m = (np.ascontiguousarray(v, dtype=np.float32) for v in (accum, m2n))
+    if a.shape != m.shape or a.ndim != 3 or a.shape[-1] != 4:
+        raise SpcbptError("adaptive_select_host: accum and m2n must be (h, w, 4) arrays of one shape")
+    h, w = a.shape[:2]
+    ty, tx = (h + 7) // 8, (w + 7) // 8
+    n = np.ascontiguousarray(tile_samples, dtype=np.uint32).reshape(-1)
+    if n.size != tx * ty:
+        raise SpcbptError(f"adaptive_select_host: tile_samples must hold {ty} x {tx} counts")
+    err = np.zeros((ty, tx), dtype=np.float32)
+    tiles = np.zeros(tx * ty, dtype=np.uint32)
+    count = C.c_int(0)
+    p = AdaptiveParams(float(target_error), int(min_samples), int(max_samples))
+    rc = lib.spcbpt_adaptive_select_host(_fp(a), _fp(m), w, h, n.ctypes.data, C.byref(p), _fp(err), tiles.ctypes.data, C.byref(count))
+    if rc != 0:
+        raise SpcbptError(f"adaptive_select_host failed ({rc})")
+    return {"error": err, "tiles": tiles[:count.value].copy()}
+
+
 def single_leaf_tree(label=0):
     t = np.zeros(1, dtype=TREE_NODE_DTYPE)
     t[0]["leaf"] = 1
@@ -826,6 +853,11 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_film_error_struct_size": [],
         "spcbpt_film_error_host": [f32p, f32p, C.c_int64, C.POINTER(FilmErrorStats)],
         "spcbpt_denoise_variance": [vp, C.POINTER(DenoiseParams)],
+        "spcbpt_adaptive_params_struct_size": [], "spcbpt_adaptive_begin": [vp, u32], "spcbpt_adaptive_end": [vp],
+        "spcbpt_adaptive_select": [vp, C.POINTER(AdaptiveParams), C.POINTER(i32)], "spcbpt_adaptive_set_tiles": [vp, vp, i32],
+        "spcbpt_launch_adaptive": [vp, C.c_char_p], "spcbpt_read_adaptive": [vp, vp, vp, vp, i32, C.POINTER(i32)],
+        "spcbpt_get_adaptive_state": [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
+        "spcbpt_adaptive_select_host": [f32p, f32p, i32, i32, vp, C.POINTER(AdaptiveParams), f32p, vp, C.POINTER(i32)],
         "spcbpt_history_capture": [vp, C.c_uint32], "spcbpt_history_reproject": [vp, C.POINTER(ReprojectParams)], "spcbpt_history_resolve": [vp, C.c_uint32],
         "spcbpt_history_reset": [vp], "spcbpt_reproject_params_struct_size": [], "spcbpt_read_history": [vp, vp, vp, vp, vp],
         "spcbpt_history_reproject_host": [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, C.POINTER(ReprojectParams), C.c_float, f32p],
@@ -901,6 +933,8 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
+    "spcbpt_adaptive_params_struct_size", "spcbpt_adaptive_begin", "spcbpt_adaptive_end", "spcbpt_adaptive_select", "spcbpt_adaptive_set_tiles", "spcbpt_launch_adaptive",
+    "spcbpt_read_adaptive", "spcbpt_get_adaptive_state", "spcbpt_adaptive_select_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
     "spcbpt_history_reproject_host", "spcbpt_history_resolve_host", "spcbpt_viewer_set_reproject", "spcbpt_viewer_get_reproject",
     "spcbpt_history_denoise", "spcbpt_read_history_variance", "spcbpt_history_reproject_var_host", "spcbpt_history_resolve_var_host", "spcbpt_history_denoise_host",
@@ -1064,6 +1098,55 @@ class Renderer:
         out = FilmErrorStats()
         self._chk(self.lib.spcbpt_film_error(self.h, C.byref(out)), "film_error")
         return out.as_dict()
+
+    # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major
+    def adaptive_begin(self, frames: int):
+        """spcbpt_adaptive_begin: the film holds the uniform subframes 0 .. frames - 1; from here on it is merged tile by tile.  Needs the
+        film's moments (set_film_moments(True) before the frames were rendered)."""
+        self._chk(self.lib.spcbpt_adaptive_begin(self.h, int(frames)), "adaptive_begin")
+
+    def adaptive_end(self):
+        """spcbpt_adaptive_end: back to ordinary launches; the film stays as it is."""
+        self._chk(self.lib.spcbpt_adaptive_end(self.h), "adaptive_end")
+
+    def adaptive_select(self, target_error, min_samples=0, max_samples=0) -> int:
+        """spcbpt_adaptive_select: lists the tiles below max_samples that have fewer than max(min_samples, 2) samples, no pixel with two
+        samples, or a mean relative standard error above target_error.  Returns the list's length."""
+        p = AdaptiveParams(float(target_error), int(min_samples), int(max_samples))
+        n = C.c_int(0)
+        self._chk(self.lib.spcbpt_adaptive_select(self.h, C.byref(p), C.byref(n)), "adaptive_select")
+        return int(n.value)
+
+    def adaptive_set_tiles(self, tiles):
+        """spcbpt_adaptive_set_tiles: imposes a tile list (strictly ascending, in range; may be empty)."""
+        t = np.asarray(tiles)
+        if t.size and (t.min() < 0 or t.max() > 0xffffffff):
+            raise SpcbptError("adaptive_set_tiles: tile indices must fit 32 unsigned bits")
+        t = np.ascontiguousarray(t, dtype=np.uint32).reshape(-1)
+        self._chk(self.lib.spcbpt_adaptive_set_tiles(self.h, t.ctypes.data if t.size else None, int(t.size)), "adaptive_set_tiles")
+
+    def launch_adaptive(self, alg: str = "SPCBPT_eye"):
+        """spcbpt_launch_adaptive: one sample for every pixel of every listed tile, each tile at its own sample index, merged into the
+        listed tiles only.  After a light pass and a sampler build, like launch("SPCBPT_eye", ...)."""
+        self._chk(self.lib.spcbpt_launch_adaptive(self.h, alg.encode()), "launch_adaptive")
+
+    def adaptive_state(self):
+        """spcbpt_get_adaptive_state: {"active", "tiles_x", "tiles_y", "n_listed"}; never waits."""
+        a, tx, ty, n = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.lib.spcbpt_get_adaptive_state(self.h, C.byref(a), C.byref(tx), C.byref(ty), C.byref(n)), "get_adaptive_state")
+        return {"active": bool(a.value), "tiles_x": int(tx.value), "tiles_y": int(ty.value), "n_listed": int(n.value)}
+
+    def read_adaptive(self):
+        """spcbpt_read_adaptive: {"samples": (tiles_y, tiles_x) uint32, "error": (tiles_y, tiles_x) float32 of the last select,
+        "tiles": the current list}."""
+        st = self.adaptive_state()
+        ty, tx = st["tiles_y"], st["tiles_x"]
+        samples = np.zeros((ty, tx), dtype=np.uint32)
+        error = np.zeros((ty, tx), dtype=np.float32)
+        tiles = np.zeros(max(1, tx * ty), dtype=np.uint32)
+        n = C.c_int(0)
+        self._chk(self.lib.spcbpt_read_adaptive(self.h, samples.ctypes.data, error.ctypes.data, tiles.ctypes.data, int(tiles.size), C.byref(n)), "read_adaptive")
+        return {"samples": samples, "error": error, "tiles": tiles[:n.value].copy()}
 
     def launch_light_batch(self, first_frame, n):
         """The light passes of launch frames first_frame .. first_frame + n - 1 as one persistent launch (spcbpt_launch_light_batch)."""

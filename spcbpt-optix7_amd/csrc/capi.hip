@@ -364,6 +364,7 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     if (w < 1 || h < 1 || (long long)w * h > (1ll << 28)) { c->error = "bad image size"; return SPCBPT_ERR_INVALID_ARG; }
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     c->deferred.active = false;   // a deferred frame of the old size is dropped with its buffer
+    c->adaptive_drop();           // adaptive sampling ends with the film its tiles belong to
     c->d_accum.release(); c->d_frame.release();
     c->free_features();           // feature buffers and denoiser planes of the old size: re-allocated on demand
     c->free_moments();            // ... and the film's second moment

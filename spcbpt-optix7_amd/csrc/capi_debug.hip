@@ -112,6 +112,7 @@ int spcbpt_clear_accum(spcbpt_ctx* c) {
     if (!c->d_accum) return SPCBPT_ERR_STATE;
     if (c->deferred.active) { c->error = "clear_accum: a deferred frame is outstanding (its merge would land in the cleared film): spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (c->sync_all()) return SPCBPT_ERR_HIP;   // merges of both render streams may still be pending
+    c->adaptive_drop();                         // adaptive sampling ends: the counts belonged to the film that is cleared
     HIP_TRY(c, hipMemsetAsync(c->d_accum, 0, (size_t)c->kp.width * c->kp.height * 16, c->rstreams[0]));
     if (c->d_m2n) HIP_TRY(c, hipMemsetAsync(c->d_m2n, 0, (size_t)c->kp.width * c->kp.height * 16, c->rstreams[0]));   // the film's second moment goes with it
     HIP_TRY(c, hipStreamSynchronize(c->rstreams[0]));

@@ -362,6 +362,24 @@ struct Context {
     int film_error(spcbpt_film_error_stats* out);
     int denoise_variance(const spcbpt_denoise_params& p);
     void free_moments();
+    // Adaptive sampling (ctx_adaptive.hip; spcbpt_adaptive_*): between adaptive_begin and adaptive_end / resize / clear_accum the film is
+    // merged tile by tile, every 8x8 tile at a sample index of its own.  Per tile of the film a count (uint32) and an error (float, with
+    // the number of pixels it is the mean of), a tile list (uint32, strictly ascending) and its length: 16 B per tile and 4 B, allocated
+    // by adaptive_begin, freed when the mode ends.  The counts live on the device only; the list's length is known to the host.
+    struct Adaptive {
+        bool active = false;
+        int tiles_x = 0, tiles_y = 0, n_listed = 0;
+        DevBuf<uint32_t> samples, known, list, n_dev;
+        DevBuf<float> error;
+        int blocks_per_cu[2] = {0, 0};   // of k_spcbpt_tiles<ENV>, by scene.general
+    } adaptive;
+    int uniform_merge_allowed(const char* what);   // SPCBPT_ERR_STATE while adaptive sampling is active: launches that merge with one weight for all pixels
+    int adaptive_begin(uint32_t frames);
+    void adaptive_drop();                          // the mode ends, the buffers go (the caller has synchronised)
+    int adaptive_select(const spcbpt_adaptive_params& ap, int* n_selected);
+    int adaptive_set_tiles(const uint32_t* tiles, int n);
+    int launch_adaptive(const char* alg);
+    int read_adaptive(uint32_t* tile_samples, float* tile_error, uint32_t* tiles, int capacity, int* n);
     // History reprojection (ctx_history.hip; spcbpt_history_*): H = (rgb, n) and G = (normal, depth) as captured, the prior R of the
     // current view, the resolved image and its RGBA8 frame -- 68 B per pixel, allocated at the first capture after a resize or a reset
     // (a resolve without a capture allocates the last two only), freed by spcbpt_resize and spcbpt_history_reset.

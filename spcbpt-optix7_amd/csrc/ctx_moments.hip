@@ -14,6 +14,7 @@ void Context::free_moments() {
 
 int Context::set_film_moments(bool on) {
     if (on == film_moments) return 0;
+    if (!on && adaptive.active) { error = "set_film_moments: adaptive sampling is active and keeps its per-pixel sample counts in the moments plane: spcbpt_adaptive_end first"; return SPCBPT_ERR_STATE; }
     if (!on) {   // the plane goes with the switch: merges that still read it may be queued
         if (sync_all()) return SPCBPT_ERR_HIP;
         free_moments();

@@ -43,6 +43,7 @@ int Context::render_done(int s) {
 }
 
 int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, int r0, int r1, int rs, bool full_mis, bool defer_merge) {
+    if (int rc = uniform_merge_allowed(defer_merge ? "launch_deferred" : "launch")) return rc;
     // (`!deferred.active`: film_ready's deferred-frame error keeps coming first, as it always has)
     if (!deferred.active && defer_merge && (full_mis || counting)) { error = "launch_deferred: plain \"pt\" / \"SPCBPT_eye\" launches only"; return SPCBPT_ERR_INVALID_ARG; }
     if (int rc = film_ready()) return rc;
@@ -137,8 +138,9 @@ int Context::sync_film() {
 }
 
 int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs) {
-    int rc = film_ready();
+    int rc = uniform_merge_allowed("launch_eye_batch");
     if (rc) return rc;
+    if ((rc = film_ready())) return rc;
     if (film_moments) {
         error = "launch_eye_batch: not with film moments enabled (spcbpt_set_film_moments): the batched merge takes up to 32 frames per pixel in one "
                 "pass and keeps no second moment (use spcbpt_launch per frame)";
@@ -215,7 +217,9 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
 int Context::finish_frame() {
     if (int rc = chain_wait()) return rc;
     if (film_moments) { if (int rc = moments_step()) return rc; }
+    time_begin("film_merge", rstream);   // (the kernel-time span adaptive sampling's "adaptive_merge" is compared with)
     launch_film_merge(kp, rstream);
+    time_end();
     HIP_TRY(this, hipGetLastError());
     return chain_end();
 }

@@ -13,8 +13,9 @@ namespace spc {
 // stream, waits for the set's sampler build, and records sets[eset].render so that no later light pass rewrites the set under it.
 // Event counters (spcbpt_enable_counters) are left untouched: the splat kernel charges none.
 int Context::launch_splat(uint32_t frame, int r0, int r1, int rs) {
-    int rc = film_ready();
+    int rc = uniform_merge_allowed("lt");
     if (rc) return rc;
+    if ((rc = film_ready())) return rc;
     if (kp.scene.env.valid) {
         error = "lt: not with an environment map: the directly seen sky is not sampled by this estimator, and the sky vertices of the cache "
                 "(SPCBPT_LV_DIRECTION) have no position to project";

@@ -1,5 +1,5 @@
 // The body of the eye megakernel (kernels.hip: k_spcbpt, k_spcbpt_sky), included INSIDE each __global__ function -- no #pragma once.
-// It reads the kernel's parameter `p` and the compile-time flags COUNT, BATCH, CACHE, ENV and SKY of the including kernel.  (As the
+// It reads the kernel's parameter `p` and the compile-time flags COUNT, BATCH, CACHE, ENV, SKY and TILES of the including kernel.  (As the
 // body of one force-inlined device function called by both kernels the timed forms came out with other code: the kernel argument
 // is then reached through a generic pointer, and the early passes schedule around it differently.  Included, k_spcbpt<...> is
 // compiled from the same statements as before SKY existed: tests/test_codegen_guard.py, tools/codegen_diff_symbols.py.)
@@ -44,6 +44,7 @@
 
     bool alive = false, exhausted = false;
     uint32_t pool_tile = 0;
+    uint32_t pool_sample = 0;   // TILES: the sample index of the wave's current tile (wave-uniform; what p.subframe is to the other forms)
     int pool_left = 0;
     uint32_t xy = 0;   // the pixel of the lane's path, x | y << 16: one register across the pass (the packing of `pend_xy`)
     WalkState w;
@@ -85,7 +86,11 @@
                 if (lane == (uint32_t)__ffsll((long long)idle) - 1u) t = atomicAdd(p.work_counter, 1u);
                 t = __shfl(t, __ffsll((long long)idle) - 1, 64);
                 if (t >= n_tiles) { exhausted = true; break; }
-                pool_tile = BATCH ? t % p.n_tiles : t;
+                if (TILES) {   // the queue is a list of tiles of the whole film, each at a sample index of its own (t < n_tiles = the list's length)
+                    pool_tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_list[t]);
+                    pool_sample = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.tile_samples[pool_tile]);
+                }
+                else pool_tile = BATCH ? t % p.n_tiles : t;
                 pool_fid = BATCH ? t / p.n_tiles : 0u;
                 pool_left = 64;
             }
@@ -106,7 +111,7 @@
                     alive = true;
                     has_ray = true;
                     fresh = true;
-                    w.dir = camera_ray(p, nx, ny, w.seed, BATCH ? p.frames[fid].subframe : p.subframe);
+                    w.dir = camera_ray(p, nx, ny, w.seed, TILES ? pool_sample : (BATCH ? p.frames[fid].subframe : p.subframe));
                     w.origin = ld3(p.eye);
                     w.done = false;
                     w.next_flux = mk3(0.0f);

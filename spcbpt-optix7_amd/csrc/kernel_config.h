@@ -5,6 +5,7 @@
 //   kernels_train.hip    the standalone traversal kernels and the pre-trace (TrainData) kernel
 // each with the launch_* functions kernels.h declares for its kernels).  The image-space passes beside them bring launchers of their own:
 //   kernels_reproject.hip  k_reproject / k_resolve, the history reprojection (kernels_reproject.h)
+//   kernels_adaptive.hip   k_tile_error / k_tile_select / k_film_merge_tiles, adaptive sampling (kernels_adaptive.h)
 #pragma once
 #include "device_lib.h"
 #include "kernels.h"

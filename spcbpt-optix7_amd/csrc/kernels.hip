@@ -11,6 +11,7 @@
 #include "eye_walk.h"
 #include "kernel_config.h"
 #include "kernels.h"
+#include "kernels_adaptive.h"
 
 namespace spc {
 
@@ -67,13 +68,23 @@ static_assert(STACK_LDS >= 16, "the pooled connections publish 16 dwords per eye
 template <bool COUNT, bool BATCH, bool CACHE, bool ENV = true>
 __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt(const KParams p) {
     constexpr bool SKY = false;   // escaped eye paths end unseen (__miss__BDPTVertex), as upstream
+    constexpr bool TILES = false;
 #include "eye_kernel_body.h"
 }
 // SKY: the escaped eye paths see the environment map (eye_sky_miss; spcbpt_set_environment_mode, SPCBPT_ENV_EYE_SEES_SKY) -- the timed
 // form of a scene with a sky (label caching, no counters), a kernel of its own so that the k_spcbpt forms keep their code
 template <bool BATCH>
 __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_sky(const KParams p) {
-    constexpr bool COUNT = false, CACHE = true, ENV = true, SKY = true;
+    constexpr bool COUNT = false, CACHE = true, ENV = true, SKY = true, TILES = false;
+#include "eye_kernel_body.h"
+}
+// TILES: adaptive sampling (spcbpt_launch_adaptive).  The queue is p.tile_list[0 .. p.n_tiles) instead of a tile range, and the pixels of
+// tile t draw sample p.tile_samples[t] instead of p.subframe: seed and jitter of camera_ray are those of an ordinary launch of that
+// subframe, so every sample is bit for bit the uniform renderer's.  The timed single-frame form (label caching, no counters, results
+// through film_write into p.result), a kernel of its own so that the k_spcbpt forms keep their code.
+template <bool ENV>
+__global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_tiles(const KParams p) {
+    constexpr bool COUNT = false, BATCH = false, CACHE = true, SKY = false, TILES = true;
 #include "eye_kernel_body.h"
 }
 
@@ -241,6 +252,26 @@ void launch_spcbpt_batch(const KParams& p, int max_blocks, hipStream_t s) {
     if (eye_sees_sky(p)) hipLaunchKernelGGL((k_spcbpt_sky<true>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
     else if (p.scene.general) hipLaunchKernelGGL((k_spcbpt<false, true, true, true>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
     else hipLaunchKernelGGL((k_spcbpt<false, true, true, false>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+}
+// ... and of the list-fed form: p.n_tiles is the list's length, p.tile_list / p.tile_samples the list and the film's per-tile sample indices
+int spcbpt_tiles_blocks(const KParams& p, int max_blocks) {
+    const long long tiles = (long long)p.n_tiles;
+    if (tiles <= 0) return 0;
+    long long blocks = (tiles + (EYE_BLOCK / 64) - 1) / (EYE_BLOCK / 64);
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    return (int)blocks;
+}
+void launch_spcbpt_tiles(const KParams& p, int max_blocks, hipStream_t s) {
+    const int blocks = spcbpt_tiles_blocks(p, max_blocks);
+    if (blocks <= 0 || !p.tile_list || !p.tile_samples) return;
+    if (p.scene.general) hipLaunchKernelGGL((k_spcbpt_tiles<true>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+    else hipLaunchKernelGGL((k_spcbpt_tiles<false>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+}
+int spcbpt_tiles_blocks_per_cu(bool general) {
+    int n = 0;
+    const hipError_t e = general ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_spcbpt_tiles<true>, EYE_BLOCK, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_spcbpt_tiles<false>, EYE_BLOCK, 0);
+    return e == hipSuccess && n > 0 ? n : 1;
 }
 // resident blocks per CU of the instantiation launch_spcbpt / launch_spcbpt_batch will really launch for (variant, batch, general, sky):
 // the forms differ in registers and scratch (the ENV = false form exists because of that), so each is asked for itself

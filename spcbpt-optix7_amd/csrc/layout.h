@@ -202,6 +202,9 @@ struct KParams {  // passed by value as the kernel argument block (the MyParams 
     uint32_t* spill;               // per-thread traversal stack overflow area
     int32_t spill_entries;         // entries per thread in `spill`
     uint32_t* diag;                // [0] traversal-stack entries dropped (deeper than LDS + spill): reported by the host as an error
+    // adaptive sampling (k_spcbpt_tiles only; appended, so that every other kernel finds its fields where they were)
+    const uint32_t* tile_list;     // the queue: n_tiles tiles of the whole film (x-major, row_begin = 0, row_step = 1), strictly ascending
+    const uint32_t* tile_samples;  // per tile of the film: the sample index its pixels draw next (what `subframe` is to an ordinary launch)
 };
 
 }  // namespace spc

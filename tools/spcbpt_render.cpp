@@ -12,8 +12,13 @@
 // --denoise-variance: the same with the variance-guided filter (spcbpt_denoise_variance; switches the film's moments on).
 // --target-error E [--check-every K]: switches the film's moments on and renders until spcbpt_film_error's mean is <= E (asked every K
 // frames, default 8, from the second frame on) or --frames is reached; prints the frames used and the error reached.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]
+// --adaptive (with --alg SPCBPT_eye and --target-error E) [--min-samples M] [--max-samples X] [--check-every K]: adaptive sampling.
+// max(M, 2) uniform frames, spcbpt_adaptive_begin, then rounds of spcbpt_adaptive_select followed by up to K (default 1) times (light
+// pass, sampler build, spcbpt_launch_adaptive) until the selection is empty or a tile would pass min(X, --frames) samples; prints the
+// tile-samples traced next to tiles x frames and writes the per-tile sample counts as <out>_samples.pgm (one pixel per 8x8 tile).
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,7 +57,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -61,6 +66,8 @@ int main(int argc, char** argv) {
     bool minimal = false, emissive = false, ordered_splat = false, denoise = false, features = false, denoise_variance = false;
     double target_error = 0.0;   // > 0: stop once the film's mean relative standard error is there
     int check_every = 8;
+    bool adaptive = false, check_every_given = false;
+    int min_samples = 0, max_samples = 0;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -75,10 +82,18 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-variance") denoise = denoise_variance = true;
         else if (a == "--features") features = true;
         else if (a == "--target-error" && i + 1 < argc) target_error = atof(argv[++i]);
-        else if (a == "--check-every" && i + 1 < argc) check_every = atoi(argv[++i]);
+        else if (a == "--check-every" && i + 1 < argc) { check_every = atoi(argv[++i]); check_every_given = true; }
+        else if (a == "--adaptive") adaptive = true;
+        else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
+        else if (a == "--max-samples" && i + 1 < argc) max_samples = atoi(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
+    if (adaptive && (alg != "SPCBPT_eye" || !(target_error > 0.0) || min_samples < 0 || max_samples < 0)) {
+        fprintf(stderr, "--adaptive needs --alg SPCBPT_eye and --target-error E > 0 (and non-negative --min-samples / --max-samples)\n");
+        return 1;
+    }
+    if (adaptive && !check_every_given) check_every = 1;
     spcbpt_scene_file* sf = nullptr;
     const std::string in(argv[1]);
     const bool gltf = in.size() > 5 && (in.compare(in.size() - 5, 5, ".gltf") == 0 || in.compare(in.size() - 4, 4, ".glb") == 0);
@@ -140,19 +155,46 @@ int main(int argc, char** argv) {
     printf("preprocessing: %.2f s\n", std::chrono::duration<double>(t1 - t0).count());
     spcbpt_film_error_stats reached = {0, 0.0, 0.0};
     unsigned lt_frame = 1000000;  // continues after the Q passes of the preprocessing like lt_params.launch_frame
-    for (int f = 0; f < frames; f++) {
+    // --adaptive: the uniform frames the estimate needs, then only the tiles that are still above the target
+    const int cap = adaptive ? (max_samples > 0 && max_samples < frames ? max_samples : frames) : 0;   // samples no tile passes
+    const int uniform_frames = adaptive ? std::min(cap, std::max(min_samples, 2)) : frames;
+    for (int f = 0; f < uniform_frames; f++) {
         if (alg == "SPCBPT_eye" || lt_alg) {  // launchLVCTrace (optixPathTracer.cpp:515-522)
             CHECK(ctx, spcbpt_launch(ctx, "light trace", ++lt_frame, 0, 0, 1));
             CHECK(ctx, spcbpt_build_sampler(ctx));
         }
         CHECK(ctx, spcbpt_launch(ctx, alg.c_str(), (uint32_t)f, 0, height, 1));  // launchSubframe (609-635)
         if (denoise || features) CHECK(ctx, spcbpt_launch_features(ctx, (uint32_t)f, 0, height, 1));   // the same subframe's primary rays
-        if (target_error > 0.0 && f >= 1 && ((f + 1) % check_every == 0 || f + 1 == frames)) {
+        if (!adaptive && target_error > 0.0 && f >= 1 && ((f + 1) % check_every == 0 || f + 1 == frames)) {
             CHECK(ctx, spcbpt_film_error(ctx, &reached));
             if (reached.pixels > 0 && reached.mean <= target_error) { frames = f + 1; break; }
         }
     }
-    if (target_error > 0.0) {
+    long long tile_samples_traced = 0;
+    int tiles_x = 0, tiles_y = 0;
+    if (adaptive) {
+        CHECK(ctx, spcbpt_adaptive_begin(ctx, (uint32_t)uniform_frames));
+        CHECK(ctx, spcbpt_get_adaptive_state(ctx, nullptr, &tiles_x, &tiles_y, nullptr));
+        const spcbpt_adaptive_params ap = {(float)target_error, (uint32_t)min_samples, (uint32_t)cap};
+        int level = uniform_frames, rounds = 0, launches = 0, listed = 0;   // level: no tile has more samples than this
+        while (level < cap) {
+            CHECK(ctx, spcbpt_adaptive_select(ctx, &ap, &listed));
+            if (listed == 0) break;
+            rounds++;
+            for (int k = 0; k < check_every && level < cap; k++, level++, launches++) {
+                CHECK(ctx, spcbpt_launch(ctx, "light trace", ++lt_frame, 0, 0, 1));
+                CHECK(ctx, spcbpt_build_sampler(ctx));
+                CHECK(ctx, spcbpt_launch_adaptive(ctx, "SPCBPT_eye"));
+                tile_samples_traced += listed;
+            }
+        }
+        CHECK(ctx, spcbpt_film_error(ctx, &reached));
+        const long long tiles = (long long)tiles_x * tiles_y, uniform = tiles * uniform_frames, full = tiles * frames;
+        printf("adaptive: target error %g, %d uniform frames, %d rounds, %d adaptive launches; tile-samples traced %lld of %lld (tiles x frames = %lld x %d), %.1f %%; "
+               "film error reached %.6g (max %.6g)\n", target_error, uniform_frames, rounds, launches, uniform + tile_samples_traced, full, tiles, frames,
+               100.0 * (double)(uniform + tile_samples_traced) / (double)full, reached.mean, reached.max);
+    }
+    else if (target_error > 0.0) {
         if (frames < 2) CHECK(ctx, spcbpt_film_error(ctx, &reached));
         printf("target error %g: %d frames used, error reached %.6g (max %.6g over %lld pixels)\n", target_error, frames, reached.mean, reached.max,
                (long long)reached.pixels);
@@ -165,7 +207,8 @@ int main(int argc, char** argv) {
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
-    printf("%d subframes of %s at %dx%d: %.3f s, %.2f Mpaths/s\n", frames, alg.c_str(), width, height, sec,
+    if (adaptive) printf("up to %d samples per tile of %s at %dx%d: %.3f s\n", cap, alg.c_str(), width, height, sec);
+    else printf("%d subframes of %s at %dx%d: %.3f s, %.2f Mpaths/s\n", frames, alg.c_str(), width, height, sec,
            (lt_alg ? (double)lt.num_core : (double)width * height + (alg == "SPCBPT_eye" ? lt.num_core : 0)) * frames / sec / 1e6);
     std::vector<float> accum((size_t)width * height * 4);
     std::vector<uint8_t> frame((size_t)width * height * 4);
@@ -174,6 +217,25 @@ int main(int argc, char** argv) {
     write_pfm(out + ".pfm", accum, width, height);
     write_ppm(out + ".ppm", frame, width, height);
     printf("wrote %s.pfm and %s.ppm\n", out.c_str(), out.c_str());
+    if (adaptive) {   // the sample-count plane: one pixel per 8x8 tile, top row first like the PPM
+        std::vector<uint32_t> counts((size_t)tiles_x * tiles_y);
+        CHECK(ctx, spcbpt_read_adaptive(ctx, counts.data(), nullptr, nullptr, 0, nullptr));
+        uint32_t top = 1;
+        for (uint32_t v : counts) top = std::max(top, v);
+        if (top > 65535u) top = 65535u;
+        const std::string path = out + "_samples.pgm";
+        FILE* f = fopen(path.c_str(), "wb");
+        if (!f) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        fprintf(f, "P5\n%d %d\n%u\n", tiles_x, tiles_y, top);
+        for (int y = tiles_y - 1; y >= 0; y--)
+            for (int x = 0; x < tiles_x; x++) {
+                const uint32_t v = std::min(counts[(size_t)y * tiles_x + x], top);
+                const uint8_t b[2] = {(uint8_t)(v >> 8), (uint8_t)(v & 255u)};
+                if (top > 255u) fwrite(b, 1, 2, f); else fwrite(b + 1, 1, 1, f);
+            }
+        fclose(f);
+        printf("wrote %s (samples per 8x8 tile, %d x %d tiles, at most %u)\n", path.c_str(), tiles_x, tiles_y, top);
+    }
     if (denoise) {
         CHECK(ctx, spcbpt_read_denoised(ctx, accum.data(), frame.data()));
         write_pfm(out + "_denoised.pfm", accum, width, height);
