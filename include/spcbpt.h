@@ -545,6 +545,58 @@ int spcbpt_film_error(spcbpt_ctx* ctx, spcbpt_film_error_stats* out);
 /* The same over caller arrays on the host (float4 per pixel each), pixels in index order.  SPCBPT_ERR_INVALID_ARG as above. */
 int spcbpt_film_error_host(const float* accum_rgba, const float* m2n, int64_t n_pixels, spcbpt_film_error_stats* out);
 
+/* Bucket film (no reference counterpart), opt-in: spcbpt_set_film_buckets(ctx, K) with K = 0 (off, the default) or 3 .. 32.  Off, a
+ * context keeps its footprint, its launches and its film bits.  On, the context keeps K float4 planes in the film's row order,
+ * bucket-major [K][height][width],
+ *   bucket_b(p) = (mean_r, mean_g, mean_b, n),
+ * and every film merge of spcbpt_launch ("pt", "SPCBPT_eye", "SPCBPT_no_rmis", "lt") and of spcbpt_merge_deferred(ctx, 1) is preceded
+ * on its stream by an update of the pixels it is about to rewrite (the rows of the launch's 8-row bands), from the frame's sample x,
+ * into bucket b = subframe % K:
+ *   subframe == 0:  every bucket of the pixel = (0, 0, 0, 0), then bucket 0 = (x, 1)   (the film overwrites on subframe 0, so the
+ *                                                                                        buckets restart)
+ *   subframe  > 0:  n' = n_b + 1,  a = 1 / n',  mean_b' = mean_b + a (x - mean_b) per channel,  n_b = n'
+ * Independent of the moments switch; switched on in mid-film, the buckets count the merges since.  A dropped deferred frame updates
+ * nothing.  The planes (16 K B per pixel) are allocated and zeroed at the first merge after spcbpt_resize, freed by spcbpt_resize
+ * (K stays), by switching off and by changing K (both wait for the context's streams), zeroed by spcbpt_clear_accum.  While the
+ * buckets are on, spcbpt_launch_eye_batch (its merge takes up to 32 frames per pixel in one pass) and spcbpt_adaptive_begin (its
+ * per-tile merge fills no buckets) return SPCBPT_ERR_STATE with a text that names the buckets; while adaptive sampling is active,
+ * spcbpt_set_film_buckets returns SPCBPT_ERR_STATE.  Any other K: SPCBPT_ERR_INVALID_ARG.  The N-GPU host (spcbpt_mgpu.h), the
+ * viewer and the checkpoints do not use the switch.  The kernel-time span of the updates is "buckets". */
+int spcbpt_set_film_buckets(spcbpt_ctx* ctx, int buckets);
+int spcbpt_get_film_buckets(spcbpt_ctx* ctx, int* buckets);
+/* Host copy of the K planes, K x height x width x 4 floats (zeros before the first merge); waits like spcbpt_read_accum.
+ * SPCBPT_ERR_STATE while the buckets are off. */
+int spcbpt_read_film_buckets(spcbpt_ctx* ctx, float* out);
+/* One update of n_pixels pixels on the host: the per-pixel function the kernel runs (float32, no contraction) on the frame's samples
+ * (float4 per pixel) and the planes [buckets][n_pixels] float4, updated in place.  No context and no GPU needed.
+ * SPCBPT_ERR_INVALID_ARG for a NULL pointer, buckets outside 3 .. 32 or n_pixels outside 1 .. 2^28. */
+int spcbpt_film_buckets_update_host(const float* sample_rgba, uint32_t subframe, int buckets, int64_t n_pixels, float* planes_inout);
+
+/* Robust resolve: a median of means over the pixel's buckets that trims as much as the buckets disagree.  Per pixel, float32, no
+ * contraction, every sum over the buckets in ascending index:
+ *   live buckets: n_i > 0, k of them (k == 0: the output is (0, 0, 0, 0));   y_i = 0.3 r_i + 0.6 g_i + 0.1 b_i
+ *   rank_i = the number of live j with y_j < y_i, or y_j == y_i and j < i
+ *   T = sum y_i,   N = sum (float)(2 rank_i - k + 1) y_i
+ *   G = 0 if k < 3 or !(T > 0), else N / ((float)k T) clamped to [0, 1]       (the Gini coefficient of the bucket luminances)
+ *   t = ((strength G) (float)k) 0.5f,   d = min((k - 1) / 2, (int)floorf(t))
+ *   kept: d <= rank_i < k - d;   rgb = sum n_i mean_i / sum n_i over the kept buckets;   w = (float)(k - 2 d)
+ * The output plane holds (r, g, b, w).  G = 0 (all buckets agree, or strength = 0) gives the film's mean, G -> (k - 1) / k (one
+ * bucket holds everything) the median bucket or buckets.  The estimator is BIASED wherever a pixel's true distribution is skewed:
+ * a symmetric trim of the bucket means of a right-skewed variable darkens it; strength is the dial and 0 is the film.
+ * The robust image is for display and for driving decisions; it does not replace accum.
+ * spcbpt_robust_resolve writes a float4 plane and its RGBA8 tone map (the film's), read by spcbpt_read_robust (either pointer may be
+ * NULL; it waits like spcbpt_read_accum; SPCBPT_ERR_STATE before the first resolve since spcbpt_resize / spcbpt_set_film_buckets).
+ * It is a link of the film-merge chain like spcbpt_denoise and leaves accum, frame, the buckets and the moments untouched.  With the
+ * buckets on but no merge yet the output is zeros (tone-mapped: opaque black).  strength must be a number in [0, 8], otherwise
+ * SPCBPT_ERR_INVALID_ARG; SPCBPT_ERR_STATE while the buckets are off, before spcbpt_resize or while a deferred frame is outstanding.
+ * The kernel-time span is "robust_resolve". */
+int spcbpt_robust_resolve(spcbpt_ctx* ctx, float strength);
+int spcbpt_read_robust(spcbpt_ctx* ctx, float* rgba, uint32_t* frame);
+/* The same resolve over caller arrays on the host: planes [buckets][n_pixels] float4 as spcbpt_read_film_buckets gives them, out_rgba
+ * float4 per pixel.  SPCBPT_ERR_INVALID_ARG for a NULL pointer, buckets outside 3 .. 32, n_pixels outside 1 .. 2^28 or a strength
+ * outside [0, 8]. */
+int spcbpt_robust_resolve_host(const float* planes, int buckets, int64_t n_pixels, float strength, float* out_rgba);
+
 /* Adaptive sampling (no reference counterpart), opt-in: trace only the tiles of the film that are still above a target error.  A TILE
  * is an 8x8 pixel block of the whole film, numbered x-major: tile t covers x = (t % tiles_x) 8 ..., y = (t / tiles_x) 8 ... with
  * tiles_x = ceil(width / 8); edge tiles are partial.  The adaptive state of a context is a sample count per tile (uint32), an error
@@ -928,7 +980,7 @@ int spcbpt_lvc_import_wait(spcbpt_ctx* ctx);
 
 /* Kernel timing measured with HIP events on the context's stream: average
  * milliseconds per launch of `name` since the last reset, and launch count.  (The film merge behind a render launch is the span
- * "film_merge", the moments update in front of it "moments".) */
+ * "film_merge", the moments update in front of it "moments", the bucket update "buckets".) */
 int spcbpt_kernel_time(spcbpt_ctx* ctx, const char* name, double* avg_ms, int* launches);
 int spcbpt_reset_kernel_time(spcbpt_ctx* ctx);
 int spcbpt_enable_kernel_timing(spcbpt_ctx* ctx, int enabled);

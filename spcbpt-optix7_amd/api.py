@@ -515,6 +515,37 @@ def film_moments_update_host(mean_before, sample, subframe, m2n):
     return m2n
 
 
+def film_buckets_update_host(sample, subframe, planes):
+    """spcbpt_film_buckets_update_host: one merge's update of the bucket planes `planes` ((K, ..., 4) float32, C-contiguous, updated IN
+    PLACE; K = 3 .. 32) from the frame's samples ((..., 4)): bucket subframe % K takes the sample, subframe 0 restarts all K.  The
+    per-pixel function the kernel runs; no GPU needed."""
+    lib = load_library()
+    x = np.ascontiguousarray(sample, dtype=np.float32)
+    if not (isinstance(planes, np.ndarray) and planes.dtype == np.float32 and planes.flags["C_CONTIGUOUS"]):
+        raise SpcbptError("film_buckets_update_host: planes must be a C-contiguous float32 array (it is updated in place)")
+    if planes.ndim < 2 or planes.shape[1:] != x.shape or x.shape[-1] != 4:
+        raise SpcbptError("film_buckets_update_host: sample must be (..., 4) and planes (K, ..., 4)")
+    rc = lib.spcbpt_film_buckets_update_host(_fp(x), int(subframe), planes.shape[0], x.size // 4, _fp(planes))
+    if rc != 0:
+        raise SpcbptError(f"film_buckets_update_host failed ({rc})")
+    return planes
+
+
+def robust_resolve_host(planes, strength=1.0):
+    """spcbpt_robust_resolve_host: the median-of-means resolve of bucket planes ((K, ..., 4) float32 as read_film_buckets gives them) at
+    `strength` in [0, 8].  Returns (..., 4) float32: (r, g, b, w) with w the number of buckets kept.  The per-pixel function the
+    kernel runs; no GPU needed."""
+    lib = load_library()
+    p = np.ascontiguousarray(planes, dtype=np.float32)
+    if p.ndim < 2 or p.shape[-1] != 4:
+        raise SpcbptError("robust_resolve_host: planes must be (K, ..., 4)")
+    out = np.zeros(p.shape[1:], np.float32)
+    rc = lib.spcbpt_robust_resolve_host(_fp(p), p.shape[0], out.size // 4, float(strength), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"robust_resolve_host failed ({rc})")
+    return out
+
+
 def film_error_host(accum, m2n):
     """spcbpt_film_error_host: {"pixels", "mean", "max"} of the relative standard error over the pixels with n >= 2, from (..., 4)
     float32 arrays as read_accum / read_film_moments give them.  The per-pixel function the kernel runs; no GPU needed."""
@@ -853,6 +884,13 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_film_error_struct_size": [],
         "spcbpt_film_error_host": [f32p, f32p, C.c_int64, C.POINTER(FilmErrorStats)],
         "spcbpt_denoise_variance": [vp, C.POINTER(DenoiseParams)],
+        "spcbpt_set_film_buckets": [vp, i32],
+        "spcbpt_get_film_buckets": [vp, C.POINTER(i32)],
+        "spcbpt_read_film_buckets": [vp, vp],
+        "spcbpt_film_buckets_update_host": [f32p, u32, i32, C.c_int64, f32p],
+        "spcbpt_robust_resolve": [vp, C.c_float],
+        "spcbpt_read_robust": [vp, vp, vp],
+        "spcbpt_robust_resolve_host": [f32p, i32, C.c_int64, C.c_float, f32p],
         "spcbpt_adaptive_params_struct_size": [], "spcbpt_adaptive_begin": [vp, u32], "spcbpt_adaptive_end": [vp],
         "spcbpt_adaptive_select": [vp, C.POINTER(AdaptiveParams), C.POINTER(i32)], "spcbpt_adaptive_set_tiles": [vp, vp, i32],
         "spcbpt_launch_adaptive": [vp, C.c_char_p], "spcbpt_read_adaptive": [vp, vp, vp, vp, i32, C.POINTER(i32)],
@@ -933,6 +971,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
+    "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
     "spcbpt_adaptive_params_struct_size", "spcbpt_adaptive_begin", "spcbpt_adaptive_end", "spcbpt_adaptive_select", "spcbpt_adaptive_set_tiles", "spcbpt_launch_adaptive",
     "spcbpt_read_adaptive", "spcbpt_get_adaptive_state", "spcbpt_adaptive_select_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
@@ -1098,6 +1137,38 @@ class Renderer:
         out = FilmErrorStats()
         self._chk(self.lib.spcbpt_film_error(self.h, C.byref(out)), "film_error")
         return out.as_dict()
+
+    # ---- bucket film and robust resolve (spcbpt_set_film_buckets, spcbpt_robust_resolve)
+    def set_film_buckets(self, k: int):
+        """spcbpt_set_film_buckets: keep K per-pixel bucket means of the film (16 K B per pixel, one small kernel per merge); K = 0
+        switches off, 3 .. 32 on."""
+        self._chk(self.lib.spcbpt_set_film_buckets(self.h, int(k)), "set_film_buckets")
+
+    def film_buckets(self) -> int:
+        v = C.c_int32()
+        self._chk(self.lib.spcbpt_get_film_buckets(self.h, C.byref(v)), "get_film_buckets")
+        return int(v.value)
+
+    def read_film_buckets(self):
+        """(K, h, w, 4) float32: (mean_r, mean_g, mean_b, n) per bucket and pixel (spcbpt_read_film_buckets)."""
+        k = self.film_buckets()
+        self.image_size()
+        out = np.zeros((max(k, 1), self.height, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_film_buckets(self.h, out.ctypes.data), "read_film_buckets")
+        return out
+
+    def robust_resolve(self, strength=1.0):
+        """spcbpt_robust_resolve: the median-of-means image of the bucket film, trimmed by `strength` in [0, 8] times the Gini
+        coefficient of the pixel's bucket luminances (0 is the film's mean).  Read with read_robust(); the film is not touched."""
+        self._chk(self.lib.spcbpt_robust_resolve(self.h, float(strength)), "robust_resolve")
+
+    def read_robust(self):
+        """(rgbw float32, rgba8): the result of the last robust_resolve() -- w the number of buckets kept -- and its tone-mapped frame."""
+        self.image_size()
+        d = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        f = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._chk(self.lib.spcbpt_read_robust(self.h, d.ctypes.data, f.ctypes.data), "read_robust")
+        return d, f
 
     # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major
     def adaptive_begin(self, frames: int):

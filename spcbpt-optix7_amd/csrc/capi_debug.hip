@@ -115,6 +115,7 @@ int spcbpt_clear_accum(spcbpt_ctx* c) {
     c->adaptive_drop();                         // adaptive sampling ends: the counts belonged to the film that is cleared
     HIP_TRY(c, hipMemsetAsync(c->d_accum, 0, (size_t)c->kp.width * c->kp.height * 16, c->rstreams[0]));
     if (c->d_m2n) HIP_TRY(c, hipMemsetAsync(c->d_m2n, 0, (size_t)c->kp.width * c->kp.height * 16, c->rstreams[0]));   // the film's second moment goes with it
+    if (c->d_buckets) HIP_TRY(c, hipMemsetAsync(c->d_buckets, 0, (size_t)c->kp.width * c->kp.height * 16 * (size_t)c->film_buckets, c->rstreams[0]));   // ... and the bucket film
     HIP_TRY(c, hipStreamSynchronize(c->rstreams[0]));
     return SPCBPT_OK;
 }

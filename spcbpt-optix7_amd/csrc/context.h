@@ -362,6 +362,20 @@ struct Context {
     int film_error(spcbpt_film_error_stats* out);
     int denoise_variance(const spcbpt_denoise_params& p);
     void free_moments();
+    // Bucket film (ctx_buckets.hip; spcbpt_set_film_buckets, off by default): K float4 planes [K][height][width] of (mean_r, mean_g,
+    // mean_b, n), bucket subframe % K updated by k_film_buckets in front of every film merge of finish_frame, and the two planes of
+    // spcbpt_robust_resolve (float4 + RGBA8).  Allocated (zeroed) at the first merge or resolve after a resize while the switch is on,
+    // freed by spcbpt_resize, by switching off and by changing K: a context that does not ask keeps its footprint, its launches and
+    // its film bits.
+    int film_buckets = 0;                  // K: 0 (off) or 3 .. 32
+    DevBuf<float> d_buckets, d_robust;
+    DevBuf<uint32_t> d_robust_frame;
+    bool have_robust = false;              // a resolve since the planes were last freed
+    int set_film_buckets(int k);
+    int ensure_buckets(hipStream_t s);
+    int buckets_step();                    // finish_frame: the update of this launch's pixels, queued on `rstream` in front of the merge
+    int robust_resolve(float strength);
+    void free_buckets();
     // Adaptive sampling (ctx_adaptive.hip; spcbpt_adaptive_*): between adaptive_begin and adaptive_end / resize / clear_accum the film is
     // merged tile by tile, every 8x8 tile at a sample index of its own.  Per tile of the film a count (uint32) and an error (float, with
     // the number of pixels it is the mean of), a tile list (uint32, strictly ascending) and its length: 16 B per tile and 4 B, allocated

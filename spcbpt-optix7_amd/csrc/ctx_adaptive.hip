@@ -25,6 +25,7 @@ int Context::adaptive_begin(uint32_t frames) {
     if (deferred.active) { error = "adaptive_begin: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (!d_accum) { error = "adaptive_begin before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!film_moments) { error = "adaptive_begin needs the film's moments: spcbpt_set_film_moments(ctx, 1) before the frames are rendered"; return SPCBPT_ERR_STATE; }
+    if (film_buckets) { error = "adaptive_begin: not with the film's buckets on (spcbpt_set_film_buckets): the per-tile merge fills no buckets"; return SPCBPT_ERR_STATE; }
     if (kp.width >= 65536u || kp.height >= 65536u) { error = "adaptive_begin: image too large"; return SPCBPT_ERR_INVALID_ARG; }
     if (sync_all()) return SPCBPT_ERR_HIP;
     const int tx = (int)adaptive_tiles_x(kp.width), ty = (int)adaptive_tiles_y(kp.height);

@@ -146,6 +146,11 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
                 "pass and keeps no second moment (use spcbpt_launch per frame)";
         return SPCBPT_ERR_STATE;
     }
+    if (film_buckets) {
+        error = "launch_eye_batch: not with the film's buckets on (spcbpt_set_film_buckets): the batched merge takes up to 32 frames per pixel in one "
+                "pass and fills no buckets (use spcbpt_launch per frame)";
+        return SPCBPT_ERR_STATE;
+    }
     if (!have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
     if (n < 1 || n > kMaxBatchFrames || !subframes) { error = "launch_eye_batch: 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
     if (n > (int)built_sets.size()) { error = "launch_eye_batch: fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }
@@ -217,6 +222,7 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
 int Context::finish_frame() {
     if (int rc = chain_wait()) return rc;
     if (film_moments) { if (int rc = moments_step()) return rc; }
+    if (film_buckets) { if (int rc = buckets_step()) return rc; }   // ... and with the bucket film on, the sample's bucket (ctx_buckets.hip)
     time_begin("film_merge", rstream);   // (the kernel-time span adaptive sampling's "adaptive_merge" is compared with)
     launch_film_merge(kp, rstream);
     time_end();

@@ -16,7 +16,10 @@
 // max(M, 2) uniform frames, spcbpt_adaptive_begin, then rounds of spcbpt_adaptive_select followed by up to K (default 1) times (light
 // pass, sampler build, spcbpt_launch_adaptive) until the selection is empty or a tile would pass min(X, --frames) samples; prints the
 // tile-samples traced next to tiles x frames and writes the per-tile sample counts as <out>_samples.pgm (one pixel per 8x8 tile).
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--out prefix]
+// --robust K [--robust-strength S]: the bucket film (spcbpt_set_film_buckets(ctx, K), K = 3 .. 32) beside the film and one
+// spcbpt_robust_resolve (strength S in [0, 8], default 1) after the last frame; writes <out>_robust.pfm / .ppm next to the usual files.
+// Not with --adaptive (the per-tile merge fills no buckets).
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -57,7 +60,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -68,6 +71,8 @@ int main(int argc, char** argv) {
     int check_every = 8;
     bool adaptive = false, check_every_given = false;
     int min_samples = 0, max_samples = 0;
+    int robust = 0;               // > 0: the number of buckets
+    float robust_strength = 1.0f;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -86,6 +91,8 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive") adaptive = true;
         else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
         else if (a == "--max-samples" && i + 1 < argc) max_samples = atoi(argv[++i]);
+        else if (a == "--robust" && i + 1 < argc) robust = atoi(argv[++i]);
+        else if (a == "--robust-strength" && i + 1 < argc) robust_strength = (float)atof(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -94,6 +101,10 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (adaptive && !check_every_given) check_every = 1;
+    if (robust != 0 && (adaptive || robust < 3 || robust > 32)) {
+        fprintf(stderr, "--robust K needs K in 3 .. 32 and no --adaptive\n");
+        return 1;
+    }
     spcbpt_scene_file* sf = nullptr;
     const std::string in(argv[1]);
     const bool gltf = in.size() > 5 && (in.compare(in.size() - 5, 5, ".gltf") == 0 || in.compare(in.size() - 4, 4, ".glb") == 0);
@@ -141,6 +152,7 @@ int main(int argc, char** argv) {
     }
     const bool moments = denoise_variance || target_error > 0.0;
     if (moments) CHECK(ctx, spcbpt_set_film_moments(ctx, 1));
+    if (robust) CHECK(ctx, spcbpt_set_film_buckets(ctx, robust));
     if (check_every < 1) check_every = 1;
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 0, 1};
     CHECK(ctx, spcbpt_set_light_trace(ctx, &lt));
@@ -204,6 +216,7 @@ int main(int argc, char** argv) {
         if (denoise_variance) CHECK(ctx, spcbpt_denoise_variance(ctx, &dp));
         else CHECK(ctx, spcbpt_denoise(ctx, &dp));
     }
+    if (robust) CHECK(ctx, spcbpt_robust_resolve(ctx, robust_strength));
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
@@ -241,6 +254,12 @@ int main(int argc, char** argv) {
         write_pfm(out + "_denoised.pfm", accum, width, height);
         write_ppm(out + "_denoised.ppm", frame, width, height);
         printf("wrote %s_denoised.pfm and %s_denoised.ppm\n", out.c_str(), out.c_str());
+    }
+    if (robust) {
+        CHECK(ctx, spcbpt_read_robust(ctx, accum.data(), reinterpret_cast<uint32_t*>(frame.data())));
+        write_pfm(out + "_robust.pfm", accum, width, height);
+        write_ppm(out + "_robust.ppm", frame, width, height);
+        printf("wrote %s_robust.pfm and %s_robust.ppm (%d buckets, strength %g)\n", out.c_str(), out.c_str(), robust, robust_strength);
     }
     if (features) {
         std::vector<float> normal_depth((size_t)width * height * 4);
