@@ -11,7 +11,7 @@
     struct alignas(16) WavePool {
         float4 ray[POOL_RAYS];      // shadow ray it * 64 + lane: direction.xyz, length (< 0: none)
         float4 org[64];             // eye vertex of lane l: position.xyz (= origin of its shadow rays), lastNormalProjection
-        int32_t slot[POOL_RAYS];    // LVC slot of connection it * 64 + lane
+        int32_t slot[POOL_RAYS];    // LVC slot of connection it * 64 + lane; bit 31: its kind (job_order.h: kJobKindBit)
         float pmf[POOL_RAYS];       // its resampling pmf (path_count * pmf2 * pmf1)
         uint8_t job[POOL_RAYS];     // before the pass: slots that hold a ray; after it: the unoccluded connections, compacted
                                     // (the pass answers a shadow ray in the ray's own slot: an occluded pair's length becomes -1 = no ray)
@@ -157,23 +157,25 @@
         cur.sub = (int)(ids_a & 1023u); cur.lastZone = (int)((ids_a >> 10) & 1023u); cur.depth = (int)(ids_a >> 20);
         cur.c.mat = (int)(ids_b & 0xffffu); cur.lsub = (int)(ids_b >> 16);
         SPC_PHASE(C_T_POOL);
-        // ---- connect the unoccluded pairs of the previous vertices.  Only ~1/4 of the 192 (lane, connection) slots of a wave
-        // hold an unoccluded pair, so the pairs are compacted into a job list and every lane -- whatever the state of its
+        // ---- connect the unoccluded pairs of the previous vertices.  Most of the 192 (lane, connection) slots of a wave hold none
+        // (on the bench workload a pass leaves ~158 jobs in ~3.2 rounds: profiles/r10_experiments.md), so the pairs are compacted
+        // into a job list and every lane -- whatever the state of its
         // own path -- evaluates one job per round: the eye vertices are published through the (now idle) traversal-stack
         // LDS, the results come back through the ray slots and each owner adds its own in connection order, which keeps
         // the floating-point sums identical to evaluating them in place.
+        // The list is ordered by kind (job_order.h): connections to surface light vertices first, to emitter vertices after them,
+        // so that whole rounds run one arm of connect_vertices only.  The kind is the bit the draw left in the slot word.
         {
-            uint32_t my_live = 0u, n_jobs = 0u;
+            uint32_t my_live = 0u, my_emitter = 0u;
 #pragma unroll
             for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
                 const bool live = has_vertex && w_ray[it * 64 + lane].w >= 0.0f;   // a ray was shot and found nothing in the way
-                const unsigned long long m = __ballot(live);
-                if (live) {
-                    w_job[n_jobs + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)(it * 64 + lane);
-                    my_live |= 1u << it;
-                }
-                n_jobs += (uint32_t)__popcll(m);
+                // (selects, no branch: with `if (live)` around the two the kernel's scratch grows from 128 to 144 B per lane)
+                my_live |= (uint32_t)live << it;
+                my_emitter |= (uint32_t)(live && w_slot[it * 64 + lane] < 0) << it;
             }
+            HwWave hw;
+            const uint32_t n_jobs = job_list_by_kind<SPCBPT_CONNECTION_N>(hw, lane, my_live, my_emitter, w_job);
             if (n_jobs != 0u) {
                 if (my_live) {  // publish this lane's eye vertex (position and lastNormalProjection already sit in w_org)
                     uint32_t* col = w_stack + lane;
@@ -212,7 +214,7 @@
                     const LightVertex* job_lvc = BATCH ? p.frames[ids >> 26].lvc_sorted : p.lvc_sorted;   // (w_slot holds the vertex's place in the sampler's order)
                     a.c.mat = (int)(col[15 * BLOCK] & 0xffffu); a.lsub = (int)(col[15 * BLOCK] >> 16);
                     LightVertex b;
-                    const float4* src = reinterpret_cast<const float4*>(job_lvc + w_slot[slot]);
+                    const float4* src = reinterpret_cast<const float4*>(job_lvc + ((uint32_t)w_slot[slot] & ~kJobKindBit));
                     const float job_pmf = w_pmf[slot];
                     float4* dst = reinterpret_cast<float4*>(&b);
 #pragma unroll
@@ -307,11 +309,16 @@
                     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) { pmf1_[it] = 1.0f; pmf2_[it] = 0.0f; u2_[it] = 0.0f; lslot_[it] = -1; bias_[it] = 0; size_[it] = 0; }
 #pragma unroll
                     for (int it = 0; it < SPCBPT_CONNECTION_N; it++) {
+                        // The connection's kind, the connect phase's scheduling hint (job_order.h): the drawn light subspace is an emitter patch's
+                        // (the light tree's labels end below them), so the vertex drawn from it sits on an emitter; 0 for the comparator.  It waits
+                        // in the slot word itself -- a register kept through the second stage is a register spilled -- and stage (3) ORs the place in.
                         if (p.uniform_lvc) {   // the comparator of BASELINE config 5: uniformSample (cuProg.h:283-289), one random number
+                            w_slot[it * 64 + lane] = 0;
                             const int vc = f_counts[0];
                             if (vc > 0) lslot_[it] = uniform_sample_index(vc, w.seed, pmf2_[it]);   // (place in the jump buffer = record of the sorted cache)
                         } else {
                             const int l = sample_first_stage<COUNT, CACHE>(p, cur.sub, w.seed, pmf1_[it], cn);
+                            w_slot[it * 64 + lane] = l >= SPCBPT_NUM_SUBSPACE - SPCBPT_NUM_SUBSPACE_LIGHTSOURCE ? (int32_t)kJobKindBit : 0;
                             const DSubspace ss = f_subspace[l];
                             if (ss.size != 0) { bias_[it] = ss.jump_bias; size_[it] = ss.size; u2_[it] = rnd(w.seed); }
                         }
@@ -326,7 +333,7 @@
                         const int lslot = lslot_[it];
                         float4 rq = make_float4(0.f, 0.f, 0.f, -1.0f);
                         if (lslot >= 0) {
-                            w_slot[it * 64 + lane] = lslot;
+                            __hip_atomic_fetch_or(&w_slot[it * 64 + lane], lslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (one ds_or_b32: the lane's own word, under its kind bit)
                             cn.add(C_CONN);
                             const float4 bq0 = reinterpret_cast<const float4*>(f_lvc + lslot)[0];
                             const float4 bq1 = reinterpret_cast<const float4*>(f_lvc + lslot)[1];

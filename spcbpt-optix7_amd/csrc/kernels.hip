@@ -9,6 +9,7 @@
 
 #include "device_lib.h"
 #include "eye_walk.h"
+#include "job_order.h"
 #include "kernel_config.h"
 #include "kernels.h"
 #include "kernels_adaptive.h"
