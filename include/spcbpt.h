@@ -895,6 +895,16 @@ int spcbpt_debug_unit(spcbpt_ctx* ctx, int op, const uint32_t* in, int in_words,
  * from one more, counting launch.  Mode 1 needs 3 x BVH depth <= 64, modes 2 / 3 <= 48 (their per-ray LDS stacks). */
 int spcbpt_debug_trace_bench(spcbpt_ctx* ctx, const float* rays, int n, int mode, int any, int repeat, float* out_t, int32_t* out_tri,
                              float* out_uv, int32_t* out_visible, double* avg_ms, uint64_t stats[5]);
+/* Per-ray entry point of the POOLED traversal pass of the eye megakernel (csrc/pool_trace.hip; tests/test_gpu_ray_verdict.py): one pass
+ * of trace_pool over n lanes, lane i being lane i % 64 of wave i / 64, in the megakernel's block, stack and hot-node table.
+ *   own_rays   n x {origin3, -, direction3, -}: the lane's own closest-hit ray, traced over (SPCBPT_SCENE_EPSILON, 1e16) where own_mask[i] != 0
+ *   shadow_org n x {position3, -}: the lane's eye vertex, the origin of its shadow rays
+ *   shadow_rays n x SPCBPT_CONNECTION_N x {direction3, length}: length < 0 = empty slot; a ray is traced over
+ *              (SPCBPT_SCENE_EPSILON, length - SPCBPT_SCENE_EPSILON).  In/out: on return the length of an OCCLUDED ray is -1.
+ *   out_t / out_tri / out_uv: n hit records (tri -1: a miss, or no own ray).
+ * Host pointers; n need not be a multiple of 64 (the last wave's other lanes hold nothing).  Returns after the kernel has run. */
+int spcbpt_debug_trace_pool(spcbpt_ctx* ctx, int n, const float* own_rays, const int32_t* own_mask, const float* shadow_org, float* shadow_rays,
+                            float* out_t, int32_t* out_tri, float* out_uv);
 /* Event counting in the kernels (off for timed runs).  1: the counting instantiations evaluate in the REFERENCE's order and charge
  * its events (two relabels per connection and one per RMIS update, a ten-probe bisection per first sampling stage): the contract's
  * byte table of SURVEY.md 8(d).  2: the instantiations the timed runs use, with counters -- the events that really execute (labels

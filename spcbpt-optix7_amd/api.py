@@ -847,6 +847,7 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_set_connection_sampler": [vp, i32],
         "spcbpt_debug_unit": [vp, i32, vp, i32, vp, i32, i32, vp, i32],
         "spcbpt_debug_trace_bench": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+        "spcbpt_debug_trace_pool": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "spcbpt_debug_spill_arm": [vp],
         "spcbpt_debug_spill_count": [vp, C.POINTER(C.c_uint64), C.POINTER(i32)],
         "spcbpt_enable_counters": [vp, i32],
@@ -965,7 +966,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_resize", "spcbpt_set_subspace", "spcbpt_set_light_trace", "spcbpt_launch", "spcbpt_launch_eye_batch", "spcbpt_launch_light_batch", "spcbpt_build_sampler", "spcbpt_build_sampler_batch",
     "spcbpt_lvc_export", "spcbpt_lvc_import", "spcbpt_lvc_set_capacity", "spcbpt_lvc_get_capacity", "spcbpt_set_environment", "spcbpt_get_environment", "spcbpt_set_environment_mode", "spcbpt_get_environment_mode", "spcbpt_hdr_load", "spcbpt_lvc_read", "spcbpt_sampler_read", "spcbpt_read_accum",
     "spcbpt_read_frame", "spcbpt_accum_device_ptr", "spcbpt_clear_accum", "spcbpt_get_counters",
-    "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench",
+    "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench", "spcbpt_debug_trace_pool",
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
     "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
@@ -1597,6 +1598,25 @@ class Renderer:
             out = (t, tri, uv)
         sd = dict(zip(("node_visits", "leaf_visits", "tri_tests", "lane_slots", "lanes_busy"), [int(x) for x in st])) if stats else None
         return out, float(ms.value), sd
+
+    def trace_pool(self, own_rays: np.ndarray, own_mask: np.ndarray, shadow_org: np.ndarray, shadow_rays: np.ndarray):
+        """spcbpt_debug_trace_pool: ONE pooled traversal pass of the eye megakernel over n lanes (lane i = lane i % 64 of wave i // 64).
+        own_rays (n, 8) [o, -, d, -] are traced where own_mask (n,) is set, over (SCENE_EPSILON, 1e16); shadow_org (n, 3 or 4) are the lanes'
+        eye vertices; shadow_rays (n, CONNECTION_N, 4) hold [direction, length], length < 0 = empty slot, traced over
+        (SCENE_EPSILON, length - SCENE_EPSILON).  Returns (t, tri, uv, lengths): the own rays' hits and the (n, CONNECTION_N) slot
+        lengths after the pass, -1 where the ray was occluded."""
+        own = np.ascontiguousarray(own_rays, dtype=np.float32).reshape(-1, 8)
+        n = own.shape[0]
+        mask = np.ascontiguousarray(own_mask, dtype=np.int32).reshape(-1)
+        org = np.zeros((n, 4), dtype=np.float32)
+        org[:, :3] = np.asarray(shadow_org, dtype=np.float32).reshape(n, -1)[:, :3]
+        sh = np.array(shadow_rays, dtype=np.float32, order="C").reshape(-1, 4)   # a copy: the call writes the answers into it
+        if mask.shape[0] != n or sh.shape[0] != n * CONNECTION_N:
+            raise ValueError("trace_pool: own_mask is (n,), shadow_rays (n, CONNECTION_N, 4)")
+        t = np.zeros(n, dtype=np.float32); tri = np.zeros(n, dtype=np.int32); uv = np.zeros((n, 2), dtype=np.float32)
+        self._chk(self.lib.spcbpt_debug_trace_pool(self.h, n, own.ctypes.data, mask.ctypes.data, org.ctypes.data, sh.ctypes.data, t.ctypes.data,
+                                                   tri.ctypes.data, uv.ctypes.data), "debug_trace_pool")
+        return t, tri, uv, sh.reshape(n, CONNECTION_N, 4)[:, :, 3].copy()
 
     # -- the reference's per-frame sequence (optixPathTracer.cpp:791-822) ------
     def render_frame(self, alg: str, subframe: int, launch_frame: Optional[int] = None, rows=None):

@@ -27,6 +27,11 @@
 #include "context.h"
 #include "kernels.h"
 namespace spc { void launch_repack_nodes_quad2(const float* nodes_q, float* out, int n_nodes, hipStream_t s); }   // quad_trace.hip (declared here: kernels.h is part of the megakernel's source hash)
+namespace spc {   // pool_trace.hip (declared here for the same reason)
+int trace_pool_debug_threads(int n);
+void launch_trace_pool_debug(const KParams& p, int n, const float* own_rays, const int32_t* own_mask, const float* shadow_org, float* shadow_rays,
+                             float* out_t, int* out_tri, float* out_uv, hipStream_t s);
+}
 #include "lbvh.h"
 #include "env_host.h"
 void spc_viewers_forget_context(spcbpt_ctx* ctx);   // viewer.cpp: called by spcbpt_destroy, so that a viewer outliving its context is safe

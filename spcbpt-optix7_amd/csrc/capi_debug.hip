@@ -362,7 +362,49 @@ int spcbpt_debug_trace_bench(spcbpt_ctx* c, const float* rays, int n, int mode, 
     return dg;
 }
 
-int spcbpt_debug_unit(spcbpt_ctx* c, int op, const uint32_t* in, int in_words, uint32_t* out, int out_words, int n, const float* aux, int aux_floats) {
+int spcbpt_debug_trace_pool(spcbpt_ctx* c, int n, const float* own_rays, const int32_t* own_mask, const float* shadow_org, float* shadow_rays,
+                            float* out_t, int32_t* out_tri, float* out_uv) {
+    CTX_CHECK(c);
+    if (n < 1 || !own_rays || !own_mask || !shadow_org || !shadow_rays || !out_t || !out_tri || !out_uv) { c->error = "debug_trace_pool: bad arguments"; return SPCBPT_ERR_INVALID_ARG; }
+    const size_t slots = (size_t)n * SPCBPT_CONNECTION_N;
+    for (size_t i = 0; i < (size_t)n; i++) {
+        bool ok = true;
+        if (own_mask[i]) for (int k = 0; k < 8; k++) if (k != 3 && k != 7) ok = ok && std::isfinite(own_rays[i * 8 + k]);
+        for (int k = 0; k < 3; k++) ok = ok && std::isfinite(shadow_org[i * 4 + k]);
+        for (size_t s = i * SPCBPT_CONNECTION_N; s < (i + 1) * SPCBPT_CONNECTION_N; s++) {
+            if (std::isnan(shadow_rays[s * 4 + 3])) ok = false;
+            if (shadow_rays[s * 4 + 3] >= 0.0f) for (int k = 0; k < 4; k++) ok = ok && std::isfinite(shadow_rays[s * 4 + k]);
+        }
+        if (!ok) { c->error = "debug_trace_pool: non-finite ray component"; return SPCBPT_ERR_INVALID_ARG; }
+    }
+    float* d_own = nullptr; int32_t* d_mask = nullptr; float* d_org = nullptr; float* d_sh = nullptr; float* d_t = nullptr; int* d_tri = nullptr; float* d_uv = nullptr;
+    auto cleanup = [&]() { dev_free(d_own); dev_free(d_mask); dev_free(d_org); dev_free(d_sh); dev_free(d_t); dev_free(d_tri); dev_free(d_uv); };
+    const int rc = c->ensure_spill((size_t)trace_pool_debug_threads(n));
+    if (rc) return rc;
+    hipError_t e = dev_alloc(&d_own, (size_t)n * 8);
+    if (e == hipSuccess) e = dev_alloc(&d_mask, (size_t)n);
+    if (e == hipSuccess) e = dev_alloc(&d_org, (size_t)n * 4);
+    if (e == hipSuccess) e = dev_alloc(&d_sh, slots * 4);
+    if (e == hipSuccess) e = dev_alloc(&d_t, (size_t)n);
+    if (e == hipSuccess) e = dev_alloc(&d_tri, (size_t)n);
+    if (e == hipSuccess) e = dev_alloc(&d_uv, (size_t)n * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_own, own_rays, (size_t)n * 32, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mask, own_mask, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_org, shadow_org, (size_t)n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sh, shadow_rays, slots * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_trace_pool_debug(c->kp, n, d_own, d_mask, d_org, d_sh, d_t, d_tri, d_uv, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess && c->sync_all()) e = hipErrorUnknown;
+    const int dg = e == hipSuccess ? c->check_diag() : 0;
+    if (e == hipSuccess) e = hipMemcpy(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(shadow_rays, d_sh, slots * 16, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) { c->error = std::string("debug_trace_pool: ") + hipGetErrorString(e); return SPCBPT_ERR_HIP; }
+    return dg;
+}
+
+int spcbpt_debug_unit(spcbpt_ctx* c, int op,const uint32_t* in, int in_words, uint32_t* out, int out_words, int n, const float* aux, int aux_floats) {
     CTX_CHECK(c);
     static const int need_in[14] = {24, 10, 2, 3, 2, 1, 52, 36, 32, 2 * SPCBPT_CONNECTION_N, 1, 4, 1, 3}, need_out[14] = {12, 1, 6, 3, 5, 3, 4, 40, 6, 4 * SPCBPT_CONNECTION_N, 24, 24, 5, 6};
     if (op < 0 || op > 13 || !in || !out || n < 0 || in_words < need_in[op] || out_words < need_out[op]) { c->error = "debug_unit: bad op or record size"; return SPCBPT_ERR_INVALID_ARG; }
