@@ -597,6 +597,70 @@ int spcbpt_read_robust(spcbpt_ctx* ctx, float* rgba, uint32_t* frame);
  * outside [0, 8]. */
 int spcbpt_robust_resolve_host(const float* planes, int buckets, int64_t n_pixels, float strength, float* out_rgba);
 
+/* Display transform (no reference counterpart), opt-in: exposure, histogram auto-exposure and a choice of tone operators, written as
+ * RGBA8 into a plane of its own.  accum, frame and every *_frame plane keep their bits; a context that never calls it keeps its
+ * footprint and its launches.  Per pixel, float32, no contraction:
+ *   L = 0.3 r + 0.6 g + 0.1 b
+ *   histogram: 256 bins over the 32 octaves [2^-16, 2^16), eight per octave, cut from L's bit pattern:
+ *     bin = (bits(L) >> 20) - ((127 - 16) << 3);   counter 256 `dark`: everything that is not >= 2^-16 (zero, negatives, NaN);
+ *     counter 257 `bright`: everything >= 2^16 (+inf included).  258 uint32 counters, their sum is the pixel count.
+ *   auto EV (double, only + - x /, so the device returns the host's bits): over the N in-range samples in ascending order drop the lowest
+ *     (uint64)(low_fraction N) and the highest (uint64)(high_fraction N) -- a bin may be cut partially --, mean = the count-weighted mean
+ *     of the kept bins' centres in log2, e + log2(1 + (m + 0.5) / 8);  target = clamp(log2(key) - mean + ev_bias, ev_min, ev_max);
+ *     EV = prev + adapt (target - prev) with a previous EV, else target.  No in-range pixel: EV = prev, or clamp(ev_bias) without one.
+ *   c' = c 2^EV, then the operator `op`:
+ *     SPCBPT_TONE_FILM      c' / (1 + L' / 1.5)                       (the curve of spcbpt_read_frame, operation for operation)
+ *     SPCBPT_TONE_REINHARD  c' (1 + L' / white^2) / (1 + L')
+ *     SPCBPT_TONE_ACES      (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14) per channel
+ *     SPCBPT_TONE_LINEAR    c'
+ *   then clamp to [0, 1], sRGB, 8 bits, alpha 255.  The RGBA8 of a pixel with a non-finite channel is unspecified beyond alpha 255.
+ * The adaptation state (the last auto EV and whether there is one) lives on the device: the exposure is computed by a kernel between the
+ * histogram and the tone map and the pass never waits for the host.  A call with manual exposure neither reads nor writes that state. */
+enum { SPCBPT_TONE_FILM = 0, SPCBPT_TONE_REINHARD = 1, SPCBPT_TONE_ACES = 2, SPCBPT_TONE_LINEAR = 3 };
+enum { SPCBPT_DISPLAY_AUTO = 1,          /* EV from the image's histogram (`ev` is ignored) */
+       SPCBPT_DISPLAY_HISTOGRAM = 2 };   /* compute the histogram under manual exposure too, for spcbpt_read_display */
+enum { SPCBPT_DISPLAY_FILM = 0, SPCBPT_DISPLAY_DENOISED = 1, SPCBPT_DISPLAY_ROBUST = 2, SPCBPT_DISPLAY_HISTORY = 3 };
+typedef struct spcbpt_display_params {
+    int32_t op;                           /* SPCBPT_TONE_* */
+    uint32_t flags;                       /* SPCBPT_DISPLAY_AUTO | SPCBPT_DISPLAY_HISTOGRAM */
+    float ev;                             /* manual exposure, in stops */
+    float key;                            /* auto: the luminance the trimmed log-mean is mapped to (> 0) */
+    float low_fraction, high_fraction;    /* auto: the shares of the in-range pixels dropped from the dark / bright end; each in [0, 1), sum < 1 */
+    float ev_bias, ev_min, ev_max;        /* auto: added to the target; the target's range (ev_min <= ev_max) */
+    float adapt;                          /* auto: the step towards the target when there is a previous EV, in (0, 1] */
+    float white;                          /* SPCBPT_TONE_REINHARD: the luminance (after exposure) that maps to white (> 0) */
+} spcbpt_display_params;
+/* op FILM, flags 0, ev 0, key 0.18, fractions 0.05 / 0.02, ev_bias 0, ev range -16 .. 16, adapt 1, white 4 */
+int spcbpt_display_default_params(spcbpt_display_params* params);
+int spcbpt_display_params_struct_size(void);   /* sizeof(spcbpt_display_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+/* The pass on one of the context's linear images: source SPCBPT_DISPLAY_FILM (accum), _DENOISED (the latest output of spcbpt_denoise /
+ * spcbpt_denoise_variance / spcbpt_history_denoise), _ROBUST (spcbpt_robust_resolve) or _HISTORY (spcbpt_history_resolve).  A link of
+ * the film-merge chain like spcbpt_robust_resolve: it sees everything queued before it.  Manual exposure is one launch; auto is a memset
+ * of the counters, the histogram, the exposure kernel and the tone map on one stream.  Writes only its own plane and record.
+ * SPCBPT_ERR_INVALID_ARG: a source or op that does not exist, unknown flag bits, fractions outside [0, 1) or summing to >= 1,
+ * ev_min > ev_max, adapt outside (0, 1], key or white not > 0, a non-finite field.  SPCBPT_ERR_STATE, with a text that names what is
+ * missing: the source image does not exist (no denoise / robust resolve / history resolve since it was last freed), before
+ * spcbpt_resize, while a deferred frame is outstanding.  The kernel-time spans are "display_hist" (memset, histogram, exposure) and
+ * "display" (the tone map). */
+int spcbpt_display(spcbpt_ctx* ctx, int source, const spcbpt_display_params* params);
+/* The same pass on an image the caller holds (float4 per pixel, any size up to 2^28 pixels): a PFM from disk, the film an N-GPU host
+ * has gathered.  The image is copied to a scratch buffer of the context before the call returns; the adaptation state is the context's.
+ * Needs no spcbpt_resize. */
+int spcbpt_display_image(spcbpt_ctx* ctx, const float* rgba, int width, int height, const spcbpt_display_params* params);
+/* What the last spcbpt_display / spcbpt_display_image left; every pointer may be NULL.  rgba8: width x height x 4 bytes of that call's
+ * image size (ask for width / height first when it is not known); histogram258: 258 uint32; ev: the EV that was applied.  Waits like
+ * spcbpt_read_accum.  SPCBPT_ERR_STATE before the first display call since spcbpt_resize, and for the histogram when the last call did
+ * not compute one (manual exposure without SPCBPT_DISPLAY_HISTOGRAM). */
+int spcbpt_read_display(spcbpt_ctx* ctx, uint8_t* rgba8, uint32_t* histogram258, float* ev, int* width, int* height);
+/* Forgets the previous EV: the next auto call jumps to its target.  Ordered behind the display calls already queued.  spcbpt_resize
+ * does the same and drops the display plane. */
+int spcbpt_display_reset(spcbpt_ctx* ctx);
+/* The same per-pixel code over caller arrays on the host: no context and no GPU needed.  have_prev / prev_ev: the adaptation state (read
+ * under SPCBPT_DISPLAY_AUTO only).  rgba8_out (n_pixels x 4 bytes), histogram_out (258 uint32; filled whatever the flags) and ev_out
+ * may each be NULL.  SPCBPT_ERR_INVALID_ARG as above, for NULL rgba / params and for n_pixels outside 1 .. 2^28. */
+int spcbpt_display_host(const float* rgba, int64_t n_pixels, const spcbpt_display_params* params, int have_prev, float prev_ev,
+                        uint8_t* rgba8_out, uint32_t* histogram_out, float* ev_out);
+
 /* Adaptive sampling (no reference counterpart), opt-in: trace only the tiles of the film that are still above a target error.  A TILE
  * is an 8x8 pixel block of the whole film, numbered x-major: tile t covers x = (t % tiles_x) 8 ..., y = (t / tiles_x) 8 ... with
  * tiles_x = ceil(width / 8); edge tiles are partial.  The adaptive state of a context is a sample count per tile (uint32), an error
@@ -990,7 +1054,8 @@ int spcbpt_lvc_import_wait(spcbpt_ctx* ctx);
 
 /* Kernel timing measured with HIP events on the context's stream: average
  * milliseconds per launch of `name` since the last reset, and launch count.  (The film merge behind a render launch is the span
- * "film_merge", the moments update in front of it "moments", the bucket update "buckets".) */
+ * "film_merge", the moments update in front of it "moments", the bucket update "buckets"; the display pass is "display_hist" and
+ * "display".) */
 int spcbpt_kernel_time(spcbpt_ctx* ctx, const char* name, double* avg_ms, int* launches);
 int spcbpt_reset_kernel_time(spcbpt_ctx* ctx);
 int spcbpt_enable_kernel_timing(spcbpt_ctx* ctx, int enabled);

@@ -57,6 +57,20 @@ class ReprojectParams(C.Structure):   # spcbpt_reproject_params
     _fields_ = [("sigma_n", C.c_float), ("sigma_x", C.c_float), ("max_history", C.c_float)]
 
 
+class DisplayParams(C.Structure):   # spcbpt_display_params
+    _fields_ = [("op", C.c_int32), ("flags", C.c_uint32), ("ev", C.c_float), ("key", C.c_float), ("low_fraction", C.c_float),
+                ("high_fraction", C.c_float), ("ev_bias", C.c_float), ("ev_min", C.c_float), ("ev_max", C.c_float), ("adapt", C.c_float),
+                ("white", C.c_float)]
+
+
+# spcbpt_display: tone operators, flag bits and sources (include/spcbpt.h)
+TONE_OPS = {"film": 0, "reinhard": 1, "aces": 2, "linear": 3}
+DISPLAY_AUTO = 1
+DISPLAY_HISTOGRAM = 2
+DISPLAY_SOURCES = {"film": 0, "denoised": 1, "robust": 2, "history": 3}
+DISPLAY_COUNTERS = 258
+
+
 class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
     _fields_ = [("pixels", C.c_int64), ("mean", C.c_double), ("max", C.c_double)]
 
@@ -546,6 +560,43 @@ def robust_resolve_host(planes, strength=1.0):
     return out
 
 
+def display_params(op="film", ev=None, auto=False, histogram=False, **fields):
+    """A spcbpt_display_params: the library's defaults (spcbpt_display_default_params), then `op` (a name of TONE_OPS or its number), the
+    flag bits from `auto` / `histogram`, a manual `ev` and any further field by name (key, low_fraction, high_fraction, ev_bias, ev_min,
+    ev_max, adapt, white, flags)."""
+    lib = load_library()
+    p = DisplayParams()
+    if lib.spcbpt_display_default_params(C.byref(p)) != 0:
+        raise SpcbptError("display_default_params failed")
+    p.op = TONE_OPS[op] if isinstance(op, str) else int(op)
+    p.flags = (DISPLAY_AUTO if auto else 0) | (DISPLAY_HISTOGRAM if histogram else 0)
+    if ev is not None:
+        p.ev = float(ev)
+    names = {n for n, _ in DisplayParams._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise SpcbptError(f"display_params: no field '{k}'")
+        setattr(p, k, v)
+    return p
+
+
+def display_host(img, have_prev=False, prev_ev=0.0, **params):
+    """spcbpt_display_host: the display transform of an (..., 4) float32 image on the host, parameters as display_params takes them.
+    Returns (rgba8 (..., 4) uint8, histogram (258,) uint32, ev).  The per-pixel code the kernels run; no GPU needed."""
+    lib = load_library()
+    x = np.ascontiguousarray(img, dtype=np.float32)
+    if x.ndim < 1 or x.shape[-1] != 4:
+        raise SpcbptError("display_host: the image must be (..., 4)")
+    p = display_params(**params)
+    out = np.zeros(x.shape, np.uint8)
+    hist = np.zeros(DISPLAY_COUNTERS, np.uint32)
+    ev = C.c_float()
+    rc = lib.spcbpt_display_host(_fp(x), x.size // 4, C.byref(p), int(bool(have_prev)), float(prev_ev), out.ctypes.data, hist.ctypes.data, C.byref(ev))
+    if rc != 0:
+        raise SpcbptError(f"display_host failed ({rc})")
+    return out, hist, float(ev.value)
+
+
 def film_error_host(accum, m2n):
     """spcbpt_film_error_host: {"pixels", "mean", "max"} of the relative standard error over the pixels with n >= 2, from (..., 4)
     float32 arrays as read_accum / read_film_moments give them.  The per-pixel function the kernel runs; no GPU needed."""
@@ -892,6 +943,13 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_robust_resolve": [vp, C.c_float],
         "spcbpt_read_robust": [vp, vp, vp],
         "spcbpt_robust_resolve_host": [f32p, i32, C.c_int64, C.c_float, f32p],
+        "spcbpt_display_default_params": [C.POINTER(DisplayParams)],
+        "spcbpt_display_params_struct_size": [],
+        "spcbpt_display": [vp, i32, C.POINTER(DisplayParams)],
+        "spcbpt_display_image": [vp, f32p, i32, i32, C.POINTER(DisplayParams)],
+        "spcbpt_read_display": [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32)],
+        "spcbpt_display_reset": [vp],
+        "spcbpt_display_host": [f32p, C.c_int64, C.POINTER(DisplayParams), i32, C.c_float, vp, vp, C.POINTER(C.c_float)],
         "spcbpt_adaptive_params_struct_size": [], "spcbpt_adaptive_begin": [vp, u32], "spcbpt_adaptive_end": [vp],
         "spcbpt_adaptive_select": [vp, C.POINTER(AdaptiveParams), C.POINTER(i32)], "spcbpt_adaptive_set_tiles": [vp, vp, i32],
         "spcbpt_launch_adaptive": [vp, C.c_char_p], "spcbpt_read_adaptive": [vp, vp, vp, vp, i32, C.POINTER(i32)],
@@ -973,6 +1031,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
+    "spcbpt_display_default_params", "spcbpt_display_params_struct_size", "spcbpt_display", "spcbpt_display_image", "spcbpt_read_display", "spcbpt_display_reset", "spcbpt_display_host",
     "spcbpt_adaptive_params_struct_size", "spcbpt_adaptive_begin", "spcbpt_adaptive_end", "spcbpt_adaptive_select", "spcbpt_adaptive_set_tiles", "spcbpt_launch_adaptive",
     "spcbpt_read_adaptive", "spcbpt_get_adaptive_state", "spcbpt_adaptive_select_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
@@ -1170,6 +1229,47 @@ class Renderer:
         f = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self._chk(self.lib.spcbpt_read_robust(self.h, d.ctypes.data, f.ctypes.data), "read_robust")
         return d, f
+
+    # ---- display transform (spcbpt_display*): exposure, histogram auto-exposure, tone operators -- an RGBA8 plane of its own
+    def display(self, source="film", **params):
+        """spcbpt_display: one of the context's linear images ("film", "denoised", "robust", "history") times 2^EV through a tone
+        operator into the display plane.  Parameters as display_params takes them: op="film" | "reinhard" | "aces" | "linear", ev=...,
+        auto=True (EV from the image's histogram, adapted on the device), histogram=True, key=..., ...  Read with read_display()."""
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        p = display_params(**params)
+        self._chk(self.lib.spcbpt_display(self.h, src, C.byref(p)), "display")
+
+    def display_image(self, img, **params):
+        """spcbpt_display_image: the same pass on an (h, w, 4) float32 image of the caller's, any size."""
+        x = np.ascontiguousarray(img, dtype=np.float32)
+        if x.ndim != 3 or x.shape[-1] != 4:
+            raise SpcbptError("display_image: the image must be (h, w, 4)")
+        p = display_params(**params)
+        self._chk(self.lib.spcbpt_display_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "display_image")
+
+    def _display_size(self):
+        w, h = C.c_int32(), C.c_int32()
+        self._chk(self.lib.spcbpt_read_display(self.h, None, None, None, C.byref(w), C.byref(h)), "read_display")
+        return int(w.value), int(h.value)
+
+    def read_display(self):
+        """(rgba8 (h, w, 4) uint8, ev): what the last display() / display_image() wrote and the EV it applied."""
+        w, h = self._display_size()
+        out = np.zeros((h, w, 4), dtype=np.uint8)
+        ev = C.c_float()
+        self._chk(self.lib.spcbpt_read_display(self.h, out.ctypes.data, None, C.byref(ev), None, None), "read_display")
+        return out, float(ev.value)
+
+    def read_display_histogram(self):
+        """(258,) uint32: the luminance histogram of the last display call's image -- 256 bins over [2^-16, 2^16), eight per octave,
+        then `dark` and `bright`.  Needs auto=True or histogram=True in that call."""
+        hist = np.zeros(DISPLAY_COUNTERS, dtype=np.uint32)
+        self._chk(self.lib.spcbpt_read_display(self.h, None, hist.ctypes.data, None, None, None), "read_display")
+        return hist
+
+    def display_reset(self):
+        """spcbpt_display_reset: forget the previous EV (the next auto call jumps to its target)."""
+        self._chk(self.lib.spcbpt_display_reset(self.h), "display_reset")
 
     # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major
     def adaptive_begin(self, frames: int):

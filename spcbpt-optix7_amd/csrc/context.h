@@ -376,6 +376,22 @@ struct Context {
     int buckets_step();                    // finish_frame: the update of this launch's pixels, queued on `rstream` in front of the merge
     int robust_resolve(float strength);
     void free_buckets();
+    // Display transform (ctx_display.hip; spcbpt_display / spcbpt_display_image, opt-in): an RGBA8 plane of its own, the device record of
+    // kernels_display.h (histogram counters + adaptation state, 1 040 B) and, for spcbpt_display_image, a scratch copy of the caller's
+    // image.  Allocated at the first call, the plane and the scratch grow-only; spcbpt_resize frees all three (and with the record the
+    // previous EV).  A context that does not ask keeps its footprint, its launches and every plane's bits.
+    DevBuf<uint32_t> d_display_frame, d_display_state;
+    DevBuf<float> d_display_src;
+    struct Display {
+        bool have = false, have_hist = false, auto_ev = false;   // of the last call
+        int width = 0, height = 0;                               // ... the size of the image it showed
+        float ev = 0.0f;                                         // ... its EV, when that was the caller's
+    } display_last;
+    int display(int source, const spcbpt_display_params& p);
+    int display_image(const float* rgba, int width, int height, const spcbpt_display_params& p);
+    int display_run(const float* src, int width, int height, const spcbpt_display_params& p);   // the launches, on `rstream` inside a chain link
+    int display_reset();
+    void free_display();
     // Adaptive sampling (ctx_adaptive.hip; spcbpt_adaptive_*): between adaptive_begin and adaptive_end / resize / clear_accum the film is
     // merged tile by tile, every 8x8 tile at a sample index of its own.  Per tile of the film a count (uint32) and an error (float, with
     // the number of pixels it is the mean of), a tile list (uint32, strictly ascending) and its length: 16 B per tile and 4 B, allocated

@@ -19,7 +19,11 @@
 // --robust K [--robust-strength S]: the bucket film (spcbpt_set_film_buckets(ctx, K), K = 3 .. 32) beside the film and one
 // spcbpt_robust_resolve (strength S in [0, 8], default 1) after the last frame; writes <out>_robust.pfm / .ppm next to the usual files.
 // Not with --adaptive (the per-tile merge fills no buckets).
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--out prefix]
+// --exposure EV | --auto-exposure [--key K], --tone film|reinhard|aces|linear: the display transform (spcbpt_display) of the last image
+// the run produced -- the robust image, else the denoised one, else the film -- at a manual EV (default 0) or at the EV measured from
+// that image's luminance histogram (key K, default 0.18), through the tone operator (default film); writes <out>_display.ppm next to
+// the usual files, which stay as they are, and prints the EV used.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -60,7 +64,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -73,6 +77,9 @@ int main(int argc, char** argv) {
     int min_samples = 0, max_samples = 0;
     int robust = 0;               // > 0: the number of buckets
     float robust_strength = 1.0f;
+    bool display = false;         // any of --exposure / --auto-exposure / --tone / --key
+    spcbpt_display_params disp;
+    spcbpt_display_default_params(&disp);
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -93,6 +100,18 @@ int main(int argc, char** argv) {
         else if (a == "--max-samples" && i + 1 < argc) max_samples = atoi(argv[++i]);
         else if (a == "--robust" && i + 1 < argc) robust = atoi(argv[++i]);
         else if (a == "--robust-strength" && i + 1 < argc) robust_strength = (float)atof(argv[++i]);
+        else if (a == "--exposure" && i + 1 < argc) { disp.ev = (float)atof(argv[++i]); display = true; }
+        else if (a == "--auto-exposure") { disp.flags |= SPCBPT_DISPLAY_AUTO; display = true; }
+        else if (a == "--key" && i + 1 < argc) { disp.key = (float)atof(argv[++i]); display = true; }
+        else if (a == "--tone" && i + 1 < argc) {
+            const std::string t = argv[++i];
+            if (t == "film") disp.op = SPCBPT_TONE_FILM;
+            else if (t == "reinhard") disp.op = SPCBPT_TONE_REINHARD;
+            else if (t == "aces") disp.op = SPCBPT_TONE_ACES;
+            else if (t == "linear") disp.op = SPCBPT_TONE_LINEAR;
+            else { fprintf(stderr, "--tone takes film, reinhard, aces or linear\n"); return 1; }
+            display = true;
+        }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -217,6 +236,8 @@ int main(int argc, char** argv) {
         else CHECK(ctx, spcbpt_denoise(ctx, &dp));
     }
     if (robust) CHECK(ctx, spcbpt_robust_resolve(ctx, robust_strength));
+    const int display_source = robust ? SPCBPT_DISPLAY_ROBUST : (denoise ? SPCBPT_DISPLAY_DENOISED : SPCBPT_DISPLAY_FILM);
+    if (display) CHECK(ctx, spcbpt_display(ctx, display_source, &disp));
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
@@ -260,6 +281,14 @@ int main(int argc, char** argv) {
         write_pfm(out + "_robust.pfm", accum, width, height);
         write_ppm(out + "_robust.ppm", frame, width, height);
         printf("wrote %s_robust.pfm and %s_robust.ppm (%d buckets, strength %g)\n", out.c_str(), out.c_str(), robust, robust_strength);
+    }
+    if (display) {
+        float ev = 0.0f;
+        CHECK(ctx, spcbpt_read_display(ctx, frame.data(), nullptr, &ev, nullptr, nullptr));
+        write_ppm(out + "_display.ppm", frame, width, height);
+        static const char* const tones[] = {"film", "reinhard", "aces", "linear"};
+        printf("wrote %s_display.ppm (%s, tone %s, %s EV %.9g)\n", out.c_str(), robust ? "the robust image" : (denoise ? "the denoised image" : "the film"), tones[disp.op],
+               (disp.flags & SPCBPT_DISPLAY_AUTO) ? "auto" : "manual", ev);
     }
     if (features) {
         std::vector<float> normal_depth((size_t)width * height * 4);
