@@ -912,15 +912,20 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *   SPCBPT_UNIT_BSEARCH  in 3: offset, size, seed (CMF = aux + offset)                                  out 3: bin, pmf, seed'
  *   SPCBPT_UNIT_STAGE2   in 2: light subspace, seed                                                     out 5: size, bin (-1: empty), LVC slot, pmf, seed'
  *   SPCBPT_UNIT_UNIFORM  in 1: seed                                                                     out 3: LVC slot, pmf, seed'
- *   SPCBPT_UNIT_CONNECT  in 52: eye vertex (spcbpt_unit_eye_vertex, 25) light vertex (spcbpt_light_vertex, 24) pad3   out 4: connectVertex_SPCBPT rgb, RMIS weight
- *   SPCBPT_UNIT_EYE_STEP in 36: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf seed ray direction3 flags(bit 0: d11) pad2
+ *   SPCBPT_UNIT_CONNECT  in 52: eye vertex (spcbpt_unit_eye_vertex, 25) light vertex (spcbpt_light_vertex, 24) form, lsub, pad
+ *                        out 4: connectVertex_SPCBPT rgb, RMIS weight; with out_words >= 5 also word 4: 1 where null_connection /
+ *                        null_connection_direction call the pair null -- the test by which the eye megakernel skips a connection
+ *                        and its shadow ray -- else 0
+ *   SPCBPT_UNIT_EYE_STEP in 36: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf seed ray direction3 flags(bit 0: d11) form, lsub
  *                        out 40: kind (0 miss, 1 surface vertex, 2 emitter front, 3 emitter back), new vertex (25), next direction3,
- *                        NextVertex.flux3, NextVertex.singlePdf, seed', done, emitter radiance3 (lightStraghtHit), t_hit, pad.
+ *                        NextVertex.flux3, NextVertex.singlePdf, seed', done, emitter radiance3 (lightStraghtHit), t_hit, and the new
+ *                        vertex's own light-tree label `lsub` as the cached forms derive it (0 in the reference form and at depth 1).
  *                        For an emitter hit the vertex words hold the LIGHT's record at the hit point, as a light sample of that
  *                        point would: position, normal, pdf = single_pdf, material_id = light id, subspace_id = its patch label.
  *   SPCBPT_UNIT_SKY_MISS in 32: last eye vertex (25) NextVertex.flux3 NextVertex.singlePdf escape direction3 (towards the sky)
  *                        out 6: contribution rgb of the eye path that sees the sky (SPCBPT_ENV_EYE_SEES_SKY), its RMIS weight
  *                        (1 / RMIS_pointer), the sky's subspace label, pad.  Needs an environment map (else SPCBPT_ERR_STATE).
+ *                        With in_words >= 34, words 32 / 33 are form / lsub.
  *   SPCBPT_UNIT_STAGE2_GUIDED in 6: CONNECTION_N light subspaces, CONNECTION_N random numbers (float bits, in [0, 1))
  *                        out 12: per connection size, bin (-1: empty subspace, skipped), place in the sorted cache (jump_bias + bin), pmf
  *                        -- the second-stage draw AS THE EYE MEGAKERNEL RUNS IT (guide table + aligned windows of eight CMF entries,
@@ -937,7 +942,21 @@ int spcbpt_set_connection_sampler(spcbpt_ctx* ctx, int mode);
  *                        out 6: tex_fetch_rgb3 (bilinear, wrap), the linearised colour3 a hit stores (powf(., 2.2f))
  * STAGE2, UNIFORM, STAGE2_GUIDED and SORTED need a built sampler, ENV and ENV_TABLE an environment map (else SPCBPT_ERR_STATE);
  * BSDF, BSEARCH, ENV, ENV_TABLE and TEX run without a subspace tuple.
- * The ray of EYE_STEP starts at the last vertex's position.  Host pointers; returns after the kernel has run. */
+ * The ray of EYE_STEP starts at the last vertex's position.  Host pointers; returns after the kernel has run.
+ * `form` (CONNECT, EYE_STEP, SKY_MISS) selects the instantiation of connect_vertices / eye_surface_hit / eye_emitter_hit /
+ * eye_sky_miss that evaluates the record -- the same text, three programs:
+ *   SPCBPT_UNIT_FORM_REFERENCE (0)     CACHE = false, ENV = true: every label by a descent of its tree, as the reference does and
+ *                                      as the counting kernels run; a record with zero pad words means what it always meant
+ *   SPCBPT_UNIT_FORM_CACHED (1)        CACHE = true, ENV = true: what the timed kernels run on a `general` scene (environment map,
+ *                                      `brdf`-flagged material, mesh light).  The eye vertex's light-tree label is the input word
+ *                                      `lsub`, the light vertex's eye-tree label the low 16 bits of its `pad` minus 1 (0: an imported
+ *                                      cache without labels, the descent happens); EYE_STEP labels the new vertex under both trees
+ *   SPCBPT_UNIT_FORM_CACHED_PLAIN (2)  CACHE = true, ENV = false: the timed kernels of a plain scene -- no direction flags, no
+ *                                      brdf division, no mesh-light branch.  SKY_MISS has no such form (SPCBPT_ERR_INVALID_ARG).
+ * What no launcher would pick is refused with SPCBPT_ERR_STATE: a cached form while the classifier trees hold direction nodes
+ * (cached labels do not depend on the direction), CACHED_PLAIN on a `general` scene.  `lsub` and the cached `pad` label index the
+ * Gamma table unchecked, as in the timed kernels: the caller keeps them in [0, SPCBPT_NUM_SUBSPACE) (the host refuses others). */
+enum { SPCBPT_UNIT_FORM_REFERENCE = 0, SPCBPT_UNIT_FORM_CACHED = 1, SPCBPT_UNIT_FORM_CACHED_PLAIN = 2 };
 typedef struct spcbpt_unit_eye_vertex {   /* the BDPTVertex fields an eye sub-path vertex carries (BDPTVertex.h:9-70) */
     float position[3], normal[3], flux[3], color[3], last_position[3], rmis3[3];
     float pdf, single_pdf, last_normal_projection;

@@ -105,6 +105,8 @@ class Oracle:
     def __init__(self, scene, nthreads: int = 0):
         self.pkg = _pkg()
         self.l = lib()
+        if getattr(scene, "mesh_lights", None):   # (its emitter triangles would reach orc_create as ordinary ones, with no light behind them)
+            raise ValueError("the oracle restates quad lights and the environment map only: a scene with mesh lights has no oracle")
         sd, self._keep = scene.desc()
         self.h = C.c_void_p(self.l.orc_create(C.byref(sd)))
         self.width = self.height = 0

@@ -21,6 +21,13 @@ CONNECTION_N = 3
 # spcbpt_set_environment_mode flags (include/spcbpt.h)
 ENV_EYE_SEES_SKY = 1
 ENV_PT_SKY_SHADOW_ALONG_DIR = 2
+# spcbpt_debug_unit: the form word of CONNECT / EYE_STEP / SKY_MISS (include/spcbpt.h: SPCBPT_UNIT_FORM_*) and where it and the eye
+# vertex's own light-tree label `lsub` sit in the input record, per op; the output words the forms add
+UNIT_FORM_REFERENCE, UNIT_FORM_CACHED, UNIT_FORM_CACHED_PLAIN = 0, 1, 2
+UNIT_FORMS = dict(reference=UNIT_FORM_REFERENCE, cached=UNIT_FORM_CACHED, cached_plain=UNIT_FORM_CACHED_PLAIN)
+UNIT_FORM_WORD = {6: 49, 7: 34, 8: 32}     # CONNECT (in 52), EYE_STEP (in 36), SKY_MISS (in 34: two words behind today's 32); lsub follows
+UNIT_CONNECT_NULL_WORD = 4                  # CONNECT with out_words >= 5: 1 where null_connection(_direction) calls the pair null
+UNIT_EYE_STEP_LSUB_WORD = 39                # EYE_STEP out: the new vertex's own light-tree label (cached forms)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libspcbpt_hip.so")

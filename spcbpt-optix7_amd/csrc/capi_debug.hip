@@ -416,6 +416,19 @@ int spcbpt_debug_unit(spcbpt_ctx* c, int op,const uint32_t* in, int in_words, ui
         for (int i = 0; i < n; i++) if (in[(size_t)i * in_words] >= (uint32_t)c->kp.scene.env.size) { c->error = "debug_unit: ENV_TABLE texel index out of range"; return SPCBPT_ERR_INVALID_ARG; }
     if (op == SPCBPT_UNIT_TEX)
         for (int i = 0; i < n; i++) if (in[(size_t)i * in_words] < 1u || in[(size_t)i * in_words] > (uint32_t)c->d_tex_data.size()) { c->error = "debug_unit: TEX texture number out of range (1 .. the scene's texture count)"; return SPCBPT_ERR_INVALID_ARG; }
+    if (op == SPCBPT_UNIT_CONNECT || op == SPCBPT_UNIT_EYE_STEP || (op == SPCBPT_UNIT_SKY_MISS && in_words >= 34)) {
+        // the form word: only what a launcher would pick for this context runs (kernels.hip: CACHE needs trees without direction
+        // nodes, ENV = false a scene that is not `general`); the cached forms index the Gamma table with `lsub` as it stands
+        const int fw = op == SPCBPT_UNIT_CONNECT ? 49 : op == SPCBPT_UNIT_EYE_STEP ? 34 : 32;
+        for (int i = 0; i < n; i++) {
+            const uint32_t form = in[(size_t)i * in_words + fw], lsub = in[(size_t)i * in_words + fw + 1];
+            if (form > (op == SPCBPT_UNIT_SKY_MISS ? SPCBPT_UNIT_FORM_CACHED : SPCBPT_UNIT_FORM_CACHED_PLAIN)) { c->error = "debug_unit: unknown form (SKY_MISS exists as reference and cached only)"; return SPCBPT_ERR_INVALID_ARG; }
+            if (form == SPCBPT_UNIT_FORM_REFERENCE) continue;
+            if (c->tree_has_direction) { c->error = "debug_unit: the cached forms need classifier trees without direction nodes (no launcher picks them for this tuple)"; return SPCBPT_ERR_STATE; }
+            if (form == SPCBPT_UNIT_FORM_CACHED_PLAIN && c->kp.scene.general != 0) { c->error = "debug_unit: the cached_plain form is the timed kernel of a plain scene; this scene is general (environment map, brdf-flagged material or mesh light)"; return SPCBPT_ERR_STATE; }
+            if (lsub >= (uint32_t)SPCBPT_NUM_SUBSPACE) { c->error = "debug_unit: lsub of a cached form is not a subspace label"; return SPCBPT_ERR_INVALID_ARG; }
+        }
+    }
     if (op == SPCBPT_UNIT_BSEARCH && (!aux || aux_floats < 1)) { c->error = "debug_unit: BSEARCH needs the CMF in aux"; return SPCBPT_ERR_INVALID_ARG; }
     if (n == 0) return SPCBPT_OK;
     if (c->sync_all()) return SPCBPT_ERR_HIP;

@@ -41,12 +41,39 @@ SPC_DEV EyeVertex load_eye_vertex(const uint32_t* w) {
     a.c.pos = ldw3(w); a.c.n = ldw3(w + 3); a.flux = ldw3(w + 6); a.c.color = ldw3(w + 9); a.c.lastPos = ldw3(w + 12); a.R3 = ldw3(w + 15);
     a.pdf = ldf(w + 18); a.singlePdf = ldf(w + 19); a.c.lnp = ldf(w + 20); a.c.lld = false;
     a.c.mat = (int)w[21]; a.sub = (int)w[22]; a.depth = (int)w[23]; a.lastZone = (int)w[24];
+    a.lsub = 0;   // the cached forms read it from a word of their own (below)
     return a;
 }
 SPC_DEV void store_eye_vertex(uint32_t* w, const EyeVertex& a) {
     stw3(w, a.c.pos); stw3(w + 3, a.c.n); stw3(w + 6, a.flux); stw3(w + 9, a.c.color); stw3(w + 12, a.c.lastPos); stw3(w + 15, a.R3);
     stf(w + 18, a.pdf); stf(w + 19, a.singlePdf); stf(w + 20, a.c.lnp);
     w[21] = (uint32_t)a.c.mat; w[22] = (uint32_t)a.sub; w[23] = (uint32_t)a.depth; w[24] = (uint32_t)a.lastZone;
+}
+
+// The `form` word of CONNECT / EYE_STEP / SKY_MISS (spcbpt.h: SPCBPT_UNIT_FORM_*): the same record through the instantiation the
+// reference-order kernels run (CACHE = false, ENV = true: word 0, the harness as it always was), the one the timed kernels run on a
+// `general` scene (CACHE = true, ENV = true) or on a plain one (CACHE = true, ENV = false).  The host has refused what no launcher
+// would pick (capi_debug.hip).
+template <bool CACHE, bool ENV>
+SPC_DEV f3 unit_connect(const KParams& p, const EyeVertex& a, const LightVertex& b, Counts<false>& cn, float* w, bool* null_pair) {
+    const bool b_dir = ENV && (b.pad & SPCBPT_LV_DIRECTION) != 0u;   // eye_kernel_body.h: the test that skips a connection and its shadow ray
+    *null_pair = b_dir ? null_connection_direction(a.c.n, ld3(b.normal)) : null_connection(a.c.pos, a.c.n, ld3(b.position), ld3(b.normal));
+    return connect_vertices<false, CACHE, ENV>(p, a, b, cn, w);
+}
+template <bool CACHE, bool ENV>
+SPC_DEV void unit_eye_step(const KParams& p, const Geom& g, const HitRec& h, f3 ray_dir, const EyeVertex& last, WalkState& w, bool d11,
+                           uint32_t* o, Counts<false>& cn) {
+    const bool last_is_origin = last.depth == 0;
+    if (g.emitter) {
+        stw3(o + 35, eye_emitter_hit<false, CACHE, ENV>(p, g, h.t, ray_dir, last_is_origin, last, w, cn));
+    } else {
+        EyeVertex mid;
+        eye_surface_hit<false, CACHE, ENV>(p, g, h.t, ray_dir, last_is_origin, last, w, mid, cn, d11);
+        o[0] = 1u;
+        store_eye_vertex(o + 1, mid);
+        stw3(o + 26, w.dir); stw3(o + 29, w.next_flux); stf(o + 32, w.next_single_pdf); o[33] = w.seed; o[34] = w.done ? 1u : 0u;
+        o[39] = (uint32_t)mid.lsub;   // the new vertex's own light-tree label (0 in the reference form, which keeps none)
+    }
 }
 
 __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const uint32_t* __restrict__ in, int in_words,
@@ -141,20 +168,26 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
         break;
     }
     case SPCBPT_UNIT_CONNECT: {
-        const EyeVertex a = load_eye_vertex(r);
+        EyeVertex a = load_eye_vertex(r);
+        a.lsub = (int)r[50];
         LightVertex b;
         uint32_t* bw = reinterpret_cast<uint32_t*>(&b);
         for (int k = 0; k < 24; k++) bw[k] = r[25 + k];
         float w = 0.0f;
-        f3 res = connect_vertices(p, a, b, cn, &w);
+        bool null_pair = false;
+        f3 res = r[49] == SPCBPT_UNIT_FORM_CACHED_PLAIN ? unit_connect<true, false>(p, a, b, cn, &w, &null_pair)
+               : r[49] == SPCBPT_UNIT_FORM_CACHED     ? unit_connect<true, true>(p, a, b, cn, &w, &null_pair)
+                                                      : unit_connect<false, true>(p, a, b, cn, &w, &null_pair);
         if (is_invalid(res)) res = mk3(0.0f);   // connectVertex_SPCBPT's own guard (raygen.cu:298)
         stw3(o, res); stf(o + 3, w);
+        if (out_words >= 5) o[4] = null_pair ? 1u : 0u;
         break;
     }
     case SPCBPT_UNIT_EYE_STEP: {
         TravStack<UBLOCK, kStackLds> st;
         st.init(s_stack, p.spill, p.spill_entries, (size_t)i, p.diag);
         EyeVertex last = load_eye_vertex(r);
+        last.lsub = (int)r[35];
         WalkState w;
         w.next_flux = ldw3(r + 25); w.next_single_pdf = ldf(r + 28); w.seed = r[29];
         w.origin = last.c.pos; w.dir = ldw3(r + 30); w.done = false;
@@ -163,34 +196,32 @@ __global__ __launch_bounds__(UBLOCK) void k_unit(const KParams p, int op, const 
         const f3 ray_dir = w.dir;
         if (!traverse<false, false>(p.scene, st, w.origin, w.dir, kEps, 1e16f, h, cn)) { o[0] = 0u; break; }   // __miss__BDPTVertex
         const Geom g = local_geometry(p.scene, h);
-        const bool last_is_origin = last.depth == 0;
+        const bool d11 = (r[33] & 1u) != 0;
+        if (r[34] == SPCBPT_UNIT_FORM_CACHED_PLAIN) unit_eye_step<true, false>(p, g, h, ray_dir, last, w, d11, o, cn);
+        else if (r[34] == SPCBPT_UNIT_FORM_CACHED) unit_eye_step<true, true>(p, g, h, ray_dir, last, w, d11, o, cn);
+        else unit_eye_step<false, true>(p, g, h, ray_dir, last, w, d11, o, cn);
+        stf(o + 38, h.t);
         if (g.emitter) {
             const DLight& L = p.scene.lights[load_pbr(p.scene, g.mat).light_id];
             const bool back = dot(ray_dir, L.type == 2 ? g.N : ld3(L.normal)) > 0;
             o[0] = back ? 3u : 2u;
-            stw3(o + 35, eye_emitter_hit(p, g, h.t, ray_dir, last_is_origin, last, w, cn));
-            stf(o + 38, h.t);
             // the light's record at the hit in the words of the (absent) new vertex: what a light sample of the same point would hold
             const LightSampleD ls = area_light_at_hit(p.scene, L, g);
             stw3(o + 1, g.P); stw3(o + 4, ls.normal); stf(o + 19, ls.pdf); stf(o + 20, ls.pdf); o[22] = (uint32_t)L.id; o[23] = (uint32_t)ls.subspace;
-        } else {
-            EyeVertex mid;
-            eye_surface_hit(p, g, h.t, ray_dir, last_is_origin, last, w, mid, cn, (r[33] & 1u) != 0);
-            o[0] = 1u;
-            store_eye_vertex(o + 1, mid);
-            stw3(o + 26, w.dir); stw3(o + 29, w.next_flux); stf(o + 32, w.next_single_pdf); o[33] = w.seed; o[34] = w.done ? 1u : 0u;
-            stf(o + 38, h.t);
         }
         break;
     }
     case SPCBPT_UNIT_SKY_MISS: {
-        const EyeVertex last = load_eye_vertex(r);
+        EyeVertex last = load_eye_vertex(r);
+        const bool cached = in_words >= 34 && r[32] == SPCBPT_UNIT_FORM_CACHED;   // (the two form words follow the 32 of the record)
+        if (cached) last.lsub = (int)r[33];
         WalkState w;
         w.next_flux = ldw3(r + 25); w.next_single_pdf = ldf(r + 28);
         w.origin = last.c.pos; w.dir = ldw3(r + 29); w.seed = 0u; w.done = false;
         float wgt = 0.0f;
         int label = -1;
-        stw3(o, eye_sky_miss(p, w.dir, last.depth == 0, last, w, cn, &wgt, &label));
+        stw3(o, cached ? eye_sky_miss<false, true, true>(p, w.dir, last.depth == 0, last, w, cn, &wgt, &label)
+                       : eye_sky_miss(p, w.dir, last.depth == 0, last, w, cn, &wgt, &label));
         stf(o + 3, wgt); o[4] = (uint32_t)label; o[5] = 0u;
         break;
     }

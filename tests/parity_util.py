@@ -88,9 +88,9 @@ def rmse(a, b):
     return float(np.sqrt(((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2).mean()))
 
 
-def grid_tree_tuple(pkg, oracle, scene, frames: int = 2, first_frame: int = 20_000):
-    """A valid multi-leaf tuple for tests: both classifiers are one position octree level (8 leaves) followed by a
-    normal split under octant 0; Q measured with those trees; Gamma rows proportional to Q."""
+def grid_trees(pkg, scene):
+    """The two classifiers of grid_tree_tuple: one position octree level (8 leaves) followed by a normal split under octant 0;
+    eye labels 101 .. 121, light labels 301 .. 321."""
     lo, hi = scene.vertices.min(0), scene.vertices.max(0)
     mid = 0.5 * (lo + hi)
 
@@ -103,8 +103,13 @@ def grid_tree_tuple(pkg, oracle, scene, frames: int = 2, first_frame: int = 20_0
         t[9]["leaf"] = 1; t[9]["label"] = base + 20
         t[10]["leaf"] = 1; t[10]["label"] = base + 21
         return t
+    return tree(100), tree(300)
 
-    et, lt = tree(100), tree(300)
+
+def grid_tree_tuple(pkg, oracle, scene, frames: int = 2, first_frame: int = 20_000):
+    """A valid multi-leaf tuple for tests: both classifiers are one position octree level (8 leaves) followed by a
+    normal split under octant 0; Q measured with those trees; Gamma rows proportional to Q."""
+    et, lt = grid_trees(pkg, scene)
     n = pkg.NUM_SUBSPACE
     uni = np.tile((np.arange(1, n + 1, dtype=np.float32) / n)[None, :], (n, 1))
     oracle.set_subspace(et, lt, np.ones(n, np.float32), uni)

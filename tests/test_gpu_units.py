@@ -339,21 +339,36 @@ def _compare_steps(ob, g, o, level, sharp_materials=()):
     return int(surf.sum()), int(emit.sum())
 
 
-def test_eye_step_connection_and_emitter_hit_chain(world, pkg, ob):
+@pytest.mark.parametrize("form", ["reference", "cached", "cached_plain"])
+def test_eye_step_connection_and_emitter_hit_chain(world, pkg, ob, form):
     """Three levels of the eye walk, every level started from the ORACLE's previous output on both sides: vertex build with the RMIS
     recursion (a8), classification (a12), emitter hits with rmis::light_hit at depth >= 2 (a10) -- then connectVertex_SPCBPT and
-    the RMIS connection weights (a15, a16) of those vertices against real light vertices, b.depth == 0 and > 0."""
-    run_chain(world, pkg, ob)
+    the RMIS connection weights (a15, a16) of those vertices against real light vertices, b.depth == 0 and > 0.  In the three forms
+    of the harness (include/spcbpt.h: SPCBPT_UNIT_FORM_*): the reference-order instantiation and the two the timed kernels run, which
+    take the labels the device passes cache; the oracle, which classifies by descent, is the yardstick of all three at the same bars."""
+    run_chain(world, pkg, ob, form=form)
 
 
-def run_chain(world, pkg, ob, sharp_materials=(), seed=8):
+def _cached_labels(ob, world, form, vertices, tree):
+    """what the device passes cache for `vertices` under tree 0 (eye) / 1 (light): the trees' own labels (no direction nodes in a trained
+    tuple, so the direction handed over is irrelevant); nothing in the reference form"""
+    if form == "reference":
+        return np.zeros(len(vertices), np.uint32)
+    pnd = np.concatenate([vertices["position"], vertices["normal"], vertices["normal"]], 1)
+    return ob.tree_index(world["tup"][tree], f32(pnd)).astype(np.uint32)
+
+
+def run_chain(world, pkg, ob, sharp_materials=(), seed=8, form="reference"):
     r, o, lvc = world["r"], world["o"], world["lvc"]
     rng = np.random.default_rng(seed)
     rec = _camera_records(pkg, ob, world, 16384, rng)
     eye_vertices, emit_total = [], 0
     for level in range(1, 5):
         want = o.eye_step(rec)
-        got = r.unit(OP["EYE_STEP"], rec.view(np.uint32).reshape(len(rec), -1), 40)
+        dev = rec.copy()                         # the form word and the previous vertex's own light-tree label (unused at depth <= 1)
+        dev["pad"][:, 0] = pkg.api.UNIT_FORMS[form]
+        dev["pad"][:, 1] = np.where(rec["last"]["depth"] >= 2, _cached_labels(ob, world, form, rec["last"], 1), 0)
+        got = r.unit(OP["EYE_STEP"], dev.view(np.uint32).reshape(len(dev), -1), 40)
         n_surf, n_emit = _compare_steps(ob, got, want, level, sharp_materials)
         emit_total += n_emit if level > 1 else 0
         go = (want["kind"] == 1) & (want["done"] == 0)
@@ -374,6 +389,10 @@ def run_chain(world, pkg, ob, sharp_materials=(), seed=8):
     words = np.zeros((n, 52), np.uint32)
     words[:, :25] = ev.view(np.uint32).reshape(n, 25)
     words[:, 25:49] = lv.view(np.uint32).reshape(n, 24)
+    if form != "reference":                      # pad = own eye-tree label + 1 on a surface vertex, as the device light pass fills it; the flag bits stay
+        words[:, 48] = (words[:, 48] & np.uint32(0xC0000000)) | np.where(lv["depth"] > 0, _cached_labels(ob, world, form, lv, 0) + 1, 0).astype(np.uint32)
+        words[:, 49] = pkg.api.UNIT_FORMS[form]
+        words[:, 50] = np.where(ev["depth"] >= 2, _cached_labels(ob, world, form, ev, 1), 0)
     out = r.unit(OP["CONNECT"], words, 4).view(np.float32)
     live = (np.abs(rgb_o).max(1) > 0)
     assert live.sum() > 0.2 * n
