@@ -290,7 +290,9 @@ int spcbpt_set_light_trace(spcbpt_ctx* ctx, const spcbpt_light_trace_params* p);
  * (8*r, height, N) and gets every N-th band.  row_begin must be a multiple of
  * 8.  For "light trace" frame is lt_params.launch_frame
  * and the row arguments are ignored.  For "pretrace" frame is
- * pr_params.iteration.  Asynchronous.
+ * pr_params.iteration.  Asynchronous.  "pretrace" draws its next-event point among the area lights (quad and mesh lights, never
+ * the environment map) and its records claim that density, 1 / (area * number of area lights); without an area light it returns
+ * SPCBPT_ERR_STATE.
  *
  * A sixth launch name, "lt": light tracing, the BDPT strategy t = 1 that upstream disables (readme.md:27).  Every vertex of the
  * light-vertex cache is connected straight to the camera and added to the pixel it lands on (spcbpt_camera_splat below gives

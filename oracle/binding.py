@@ -365,7 +365,10 @@ def tree_index(tree: np.ndarray, pnd: np.ndarray):
 # ---- preprocessing (oracle/preprocess_ref.h) --------------------------------------------------------------------
 def _pre_methods():
     def pretrace(self, iteration, num_core=10000, padding=10, nthreads=None):
-        return self.l.orc_pretrace(self.h, iteration, num_core, padding, nthreads or self.nthreads)
+        n = self.l.orc_pretrace(self.h, iteration, num_core, padding, nthreads or self.nthreads)
+        if n < 0:
+            raise RuntimeError(f"orc_pretrace -> {n}: pretrace needs at least one area light (the scene has none beside its sky)")
+        return n
 
     def train_records(self):
         p = self.pkg

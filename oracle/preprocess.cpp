@@ -35,6 +35,8 @@ int orc_set_light_trace(orc_ctx* c, int num_core, int core_padding, int m_per_co
 // launchPretrace (optixPathTracer.cpp:523-551): one "pretrace" launch + valid_sample_gather
 int orc_pretrace(orc_ctx* c, int iteration, int num_core, int padding, int nthreads) {
     PreState& st = pre_of(c);
+    // the next-event candidate is drawn among the area lights (sample_quad): a scene lit by its sky alone has none to draw
+    if ((int)c->P.scene->lights.size() - (c->P.scene->sky.valid ? 1 : 0) < 1) return SPCBPT_ERR_STATE;  // (negative: no count)
     std::vector<preTracePath> paths(num_core);
     std::vector<preTraceConnection> conns((size_t)num_core * padding);
     std::atomic<int> next(0);

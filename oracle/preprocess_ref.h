@@ -103,8 +103,9 @@ inline preTraceConnection make_conn(nVertex& a, nVertex& b) {  // pathInfo_node(
 }
 
 // PreTrace_buildPathInfo (raygen.cu:708-740)
+// light_pdf_scale: n_lights / (lights the next-event candidate is drawn among); the claimed density is the one drawn from (d16)
 inline void PreTrace_buildPathInfo(const Params& P, BDPTVertex* eye, nVertex_device light, preTracePath* path, preTraceConnection* conn,
-                                   int pathSize) {
+                                   int pathSize, float light_pdf_scale) {
     path->valid = 1;
     path->begin_ind = 0;
     path->end_ind = pathSize - 1;
@@ -113,7 +114,7 @@ inline void PreTrace_buildPathInfo(const Params& P, BDPTVertex* eye, nVertex_dev
     nVertex_device n_next_eye(P, light, n_eye, true);
     float3 seg_contri = n_eye.local_contri(P, light);
     path->sample_pdf = n_next_eye.pdf;
-    path->sample_pdf += n_eye.pdf * light.pdf;
+    path->sample_pdf += n_eye.pdf * (light.pdf * light_pdf_scale);
     path->fix_pdf = n_next_eye.pdf;
     float3 contri = eye->flux * light.forward_light(P, n_eye) * seg_contri;
     for (int i = 0; i < path->end_ind; i++) {
@@ -142,6 +143,9 @@ inline void raygen_TrainData(const Params& P, int launch_index, int iteration, i
     float3 ray_direction = normalize(dx * P.U + dy * P.V + P.W);
     float3 ray_origin = P.eye;
     BDPTVertex buffer[10];  // PRETRACE_CONN_PADDING
+    // sample_quad draws among the area lights only; lightSample::pdf divides by all lights (1 without a sky: exact)
+    const int n_area_lights = (int)S.lights.size() - (S.sky.valid ? 1 : 0);
+    const float light_pdf_scale = (float)S.lights.size() / (float)n_area_lights;
     int buffer_size = 0, resample_number = 0;
     PayloadBDPTVertex payload;
     payload.clear();
@@ -164,7 +168,7 @@ inline void raygen_TrainData(const Params& P, int launch_index, int iteration, i
                 light_sample.ReverseSample(P, S.lights[light_id], payload.path.currentVertex().uv);
                 BDPTVertex light_vertex;
                 init_vertex_from_lightSample(light_sample, light_vertex);
-                PreTrace_buildPathInfo(P, buffer + buffer_size - 1, nVertex_device(light_vertex, false), currentPath, currentConn, buffer_size);
+                PreTrace_buildPathInfo(P, buffer + buffer_size - 1, nVertex_device(light_vertex, false), currentPath, currentConn, buffer_size, light_pdf_scale);
                 resample_number++;
             }
             break;
@@ -178,7 +182,7 @@ inline void raygen_TrainData(const Params& P, int launch_index, int iteration, i
         init_vertex_from_lightSample(light_sample, light_vertex);
         if (S.visibilityTest(eye_subpath.position, light_vertex.position, P.counters) && rr_acc_accept(resample_number, payload.seed)) {
             if (dot(vis_vec, light_sample.normal()) < 0) {
-                PreTrace_buildPathInfo(P, buffer + buffer_size - 1, nVertex_device(light_vertex, false), currentPath, currentConn, buffer_size);
+                PreTrace_buildPathInfo(P, buffer + buffer_size - 1, nVertex_device(light_vertex, false), currentPath, currentConn, buffer_size, light_pdf_scale);
                 resample_number++;
             }
         }

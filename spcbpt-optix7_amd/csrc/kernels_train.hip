@@ -99,7 +99,9 @@ SPC_DEV NVertex nv_extend(const DeviceScene& S, const NVertex& a, const NVertex&
 }
 static constexpr int PRETRACE_MAX = 10;  // PRETRACE_CONN_PADDING
 
-SPC_DEV void pretrace_build_path(const DeviceScene& S, const EyeVertex* buffer, int buffer_size, NVertex light,
+// light_pdf_scale: n_lights / (the lights the next-event candidate is drawn among), so that the claimed density is the one drawn from
+// (exactly 1 without a sky)
+SPC_DEV void pretrace_build_path(const DeviceScene& S, const EyeVertex* buffer, int buffer_size, NVertex light, float light_pdf_scale,
                                  spcbpt_pretrace_path& path, spcbpt_pretrace_node* conn) {
     path.valid = 1;
     path.begin_ind = 0;
@@ -109,7 +111,7 @@ SPC_DEV void pretrace_build_path(const DeviceScene& S, const EyeVertex* buffer, 
     const NVertex n_next_eye = nv_extend(S, light, n_eye, true);
     const f3 vec = light.position - n_eye.position;
     const f3 seg_contri = bsdf_eval(nv_mat(S, n_eye), n_eye.normal, n_eye.dir, normalize(vec));  // local_contri
-    path.sample_pdf = n_next_eye.pdf + n_eye.pdf * light.pdf;
+    path.sample_pdf = n_next_eye.pdf + n_eye.pdf * (light.pdf * light_pdf_scale);
     path.fix_pdf = n_next_eye.pdf;
     f3 contri = buffer[e].flux * nv_forward_light(S, light, n_eye) * seg_contri;
     for (int i = 0; i < path.end_ind; i++) {
@@ -159,6 +161,11 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
     path.valid = 0; path.begin_ind = path.end_ind = 0; path.choice_id = 0; path.sample_pdf = path.fix_pdf = 0.0f;
     path.contri[0] = path.contri[1] = path.contri[2] = 0.0f; path.pad = 0;
     spcbpt_pretrace_node* conn = nodes + (size_t)launch_index * padding;
+    // QUAD and mesh lights only: upstream picks among all lights here too (raygen.cu:820-823) and then reads the sample's position, which
+    // the ENV branch never sets -- undefined, so the sky is left out of the training pass's next-event candidates.
+    // Context::launch_pretrace refuses a scene without an area light, so n_quads >= 1.
+    const int n_quads = S.n_lights - (S.env.valid ? 1 : 0);
+    const float light_pdf_scale = (float)S.n_lights / (float)n_quads;
     while (true) {
         HitRec h;
         if (!traverse<false, false>(S, st, w.origin, w.dir, kEps, 1e16f, h, cn)) break;
@@ -173,7 +180,7 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
                 const float r = rnd(w.seed);                                  // rr_acc_accept
                 if (1.0f / (resample_number + 1) > r) {
                     const LightSampleD ls = area_light_at_hit(S, L, g);
-                    pretrace_build_path(S, buffer, buffer_size, nv_from_light(ls), path, conn);
+                    pretrace_build_path(S, buffer, buffer_size, nv_from_light(ls), light_pdf_scale, path, conn);
                     resample_number++;
                 }
             }
@@ -184,10 +191,7 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
         eye_surface_hit(p, g, h.t, ray_dir, last.depth == 0, last, w, mid, cn);
         buffer[buffer_size] = mid;
         buffer_size++;
-        // next-event candidate
-        // QUAD and mesh lights only: upstream picks among all lights here too (raygen.cu:820-823) and then reads the sample's position, which
-        // the ENV branch never sets -- undefined, so the sky is left out of the training pass's next-event candidates
-        const int n_quads = S.n_lights - (S.env.valid ? 1 : 0);
+        // next-event candidate, among the area lights
         const int lid = min(max((int)floorf(rnd(w.seed) * n_quads), 0), n_quads - 1);
         const LightSampleD ls = area_light_sample(S, S.lights[lid], w.seed);
         const f3 vis_vec = ls.position - mid.c.pos;
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(BLOCK) void k_pretrace(const KParams p, uint32_t it
             const float r = rnd(w.seed);
             if (1.0f / (resample_number + 1) > r) {
                 if (dot(vis_vec, ls.normal) < 0) {
-                    pretrace_build_path(S, buffer, buffer_size, nv_from_light(ls), path, conn);
+                    pretrace_build_path(S, buffer, buffer_size, nv_from_light(ls), light_pdf_scale, path, conn);
                     resample_number++;
                 }
             }

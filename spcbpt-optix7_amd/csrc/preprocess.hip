@@ -24,6 +24,12 @@ int Context::set_pretrace(int num_core, int padding) {
 
 int Context::launch_pretrace(uint32_t iteration) {
     if (!have_camera || !d_accum) { error = "pretrace needs a camera and an image size (pixel ids)"; return SPCBPT_ERR_STATE; }
+    // the next-event candidate of the training pass is drawn among the area lights: a sky alone leaves none to draw
+    // (spcbpt_create refuses such a scene today; the kernel's light index must not depend on that)
+    if (kp.scene.n_lights - (kp.scene.env.valid ? 1 : 0) < 1) {
+        error = "pretrace needs at least one area light (quad or mesh light): the scene has none beside its environment map";
+        return SPCBPT_ERR_STATE;
+    }
     if (!have_subspace) { int rc = install_minimal_tuple(); if (rc) return rc; }
     if (!pre) pre = new Preprocessor();
     const size_t np = (size_t)pre_num_core, nn = np * (size_t)pre_padding;

@@ -1,5 +1,8 @@
 """Parity of the host-owned preprocessing driven through the C ABI against the oracle, stage by stage.
-Tolerances: pretrace records (device FP32 vs host FP32) within 2e-3 relative for >= 98 % of the matched records; stage 1
+Tolerances: pretrace records (device FP32 vs host FP32) within 2e-3 relative for >= 99 % and within 2e-4 for >= 93.8 % of the matched
+records -- what the conditioning of the records' own float64 definition (tests/pretrace_ref.py) leaves two FP32 implementations that
+both meet it: on the oracle's records of this very launch 0.46 % / 3.05 % of the paths have 2 (hard bar + C_KAPPA kappa) above 2e-3 /
+2e-4, and twice that share is allowed (every record is held to the definition itself by tests/test_gpu_pretrace_definition.py); stage 1
 (reweight + both trees) is pure host arithmetic on identical records -> bit-exact; Q within 2 % (different light-path FP
 flips); Gamma_0 and the trained Gamma within 2e-3 absolute on >= 99.5 % of the entries; CMF rows valid."""
 import numpy as np
@@ -32,7 +35,7 @@ def test_pretrace_records_match_oracle(gpu, pkg, ob):
     table = {}
     for i, p in enumerate(po):
         table.setdefault(key(p), []).append(i)
-    matched = good = 0
+    matched = good = fine = 0
     for p in pg:
         cands = table.get(key(p), [])
         if len(cands) != 1:
@@ -42,11 +45,12 @@ def test_pretrace_records_match_oracle(gpu, pkg, ob):
         a = np.concatenate([p["contri"], [p["sample_pdf"], p["fix_pdf"]]]).astype(np.float64)
         b = np.concatenate([q["contri"], [q["sample_pdf"], q["fix_pdf"]]]).astype(np.float64)
         na, nb = ng[p["begin_ind"]:p["end_ind"]], no[q["begin_ind"]:q["end_ind"]]
-        ok = np.allclose(a, b, rtol=2e-3, atol=1e-9) and np.allclose(na["peak_pdf"], nb["peak_pdf"], rtol=2e-3, atol=1e-12) \
-            and np.allclose(na["a_position"], nb["a_position"], atol=1e-4) and np.allclose(na["b_position"], nb["b_position"], atol=1e-4) \
+        rest = np.allclose(na["a_position"], nb["a_position"], atol=1e-4) and np.allclose(na["b_position"], nb["b_position"], atol=1e-4) \
             and (na["label_a"] == nb["label_a"]).all() and (na["label_b"] == nb["label_b"]).all() and (na["light_source"] == nb["light_source"]).all()
-        good += bool(ok)
-    assert matched >= 0.9 * len(pg) and good >= 0.98 * matched, (len(pg), matched, good)
+        close = lambda rtol: np.allclose(a, b, rtol=rtol, atol=1e-9) and np.allclose(na["peak_pdf"], nb["peak_pdf"], rtol=rtol, atol=1e-12)
+        good += bool(rest and close(2e-3))
+        fine += bool(rest and close(2e-4))
+    assert matched >= 0.9 * len(pg) and good >= 0.99 * matched and fine >= 0.938 * matched, (len(pg), matched, good, fine)
 
 
 def test_preprocessing_stages_match_oracle(gpu, pkg, ob):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from tests.parity_util import rmse
+from tests.pretrace_ref import check_invariants
 
 
 def _oracle(ob, pkg, scene, w, h, lt=(2000, 64, 1)):
@@ -29,22 +30,10 @@ def test_pretrace_records_invariants(ob, pkg):
     n_valid = o.pretrace(1, 3000)
     paths, nodes = o.train_records()
     assert n_valid == len(paths) and 0.2 * 3000 < n_valid <= 3000
-    assert (paths["valid"] == 1).all() and (nodes["valid"] == 1).all()
-    assert paths["begin_ind"][0] == 0 and (paths["begin_ind"][1:] == paths["end_ind"][:-1]).all() and paths["end_ind"][-1] == len(nodes)
-    k = paths["end_ind"] - paths["begin_ind"]
-    assert k.min() >= 1 and k.max() <= 9           # eye surface vertices per path, padding 10 incl. the camera
-    assert (nodes["path_id"] == np.repeat(np.arange(len(paths)), k)).all()
-    # label_a carries the eye depth 1..k until the trees exist (set_eye_depth)
-    assert (nodes["label_a"] == np.concatenate([np.arange(1, kk + 1) for kk in k])).all()
-    # the last node of a path joins the last eye vertex with the emitter vertex; the others have surface B vertices
-    last = paths["end_ind"] - 1
-    assert (nodes["light_source"][last] == 1).all()
-    inner = np.ones(len(nodes), bool); inner[last] = False
-    assert (nodes["light_source"][inner] == 0).all()
-    assert (nodes["label_b"][last] >= 900).all()   # emitter patch ids of the single divLevel-10 light
-    assert np.isfinite(nodes["peak_pdf"]).all() and (nodes["peak_pdf"] >= 0).all()
-    assert np.isfinite(paths["contri"]).all() and (paths["sample_pdf"] >= paths["fix_pdf"]).all()
-    assert (paths["pixel_id"] >= 0).all() and (paths["pixel_id"] < 64).all()
+    # the invariants of every gathered record set (shared with tests/test_pretrace_definition_cpu.py), with the Cornell box's own:
+    # the single divLevel-10 light's patch ids, and a next-event density that dominates (sample_pdf >= fix_pdf)
+    k = check_invariants(paths, nodes, 64, 64, padding=10, emitter_label_min=900, sample_pdf_above_fix_pdf=True)
+    assert k.max() <= 9                            # eye surface vertices per path, padding 10 incl. the camera
     # a second launch appends with re-based indices (valid_sample_gather)
     o.pretrace(2, 3000)
     p2, n2 = o.train_records()
