@@ -621,7 +621,8 @@ int spcbpt_robust_resolve_host(const float* planes, int buckets, int64_t n_pixel
 enum { SPCBPT_TONE_FILM = 0, SPCBPT_TONE_REINHARD = 1, SPCBPT_TONE_ACES = 2, SPCBPT_TONE_LINEAR = 3 };
 enum { SPCBPT_DISPLAY_AUTO = 1,          /* EV from the image's histogram (`ev` is ignored) */
        SPCBPT_DISPLAY_HISTOGRAM = 2 };   /* compute the histogram under manual exposure too, for spcbpt_read_display */
-enum { SPCBPT_DISPLAY_FILM = 0, SPCBPT_DISPLAY_DENOISED = 1, SPCBPT_DISPLAY_ROBUST = 2, SPCBPT_DISPLAY_HISTORY = 3 };
+enum { SPCBPT_DISPLAY_FILM = 0, SPCBPT_DISPLAY_DENOISED = 1, SPCBPT_DISPLAY_ROBUST = 2, SPCBPT_DISPLAY_HISTORY = 3,
+       SPCBPT_DISPLAY_BLOOM = 4 };       /* spcbpt_display only: the bloom plane (spcbpt_bloom, below) */
 typedef struct spcbpt_display_params {
     int32_t op;                           /* SPCBPT_TONE_* */
     uint32_t flags;                       /* SPCBPT_DISPLAY_AUTO | SPCBPT_DISPLAY_HISTOGRAM */
@@ -636,7 +637,8 @@ typedef struct spcbpt_display_params {
 int spcbpt_display_default_params(spcbpt_display_params* params);
 int spcbpt_display_params_struct_size(void);   /* sizeof(spcbpt_display_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
 /* The pass on one of the context's linear images: source SPCBPT_DISPLAY_FILM (accum), _DENOISED (the latest output of spcbpt_denoise /
- * spcbpt_denoise_variance / spcbpt_history_denoise), _ROBUST (spcbpt_robust_resolve) or _HISTORY (spcbpt_history_resolve).  A link of
+ * spcbpt_denoise_variance / spcbpt_history_denoise), _ROBUST (spcbpt_robust_resolve), _HISTORY (spcbpt_history_resolve) or _BLOOM (the
+ * plane spcbpt_bloom / spcbpt_bloom_image left, at that plane's own size; SPCBPT_ERR_STATE naming spcbpt_bloom without one).  A link of
  * the film-merge chain like spcbpt_robust_resolve: it sees everything queued before it.  Manual exposure is one launch; auto is a memset
  * of the counters, the histogram, the exposure kernel and the tone map on one stream.  Writes only its own plane and record.
  * SPCBPT_ERR_INVALID_ARG: a source or op that does not exist, unknown flag bits, fractions outside [0, 1) or summing to >= 1,
@@ -662,6 +664,50 @@ int spcbpt_display_reset(spcbpt_ctx* ctx);
  * may each be NULL.  SPCBPT_ERR_INVALID_ARG as above, for NULL rgba / params and for n_pixels outside 1 .. 2^28. */
 int spcbpt_display_host(const float* rgba, int64_t n_pixels, const spcbpt_display_params* params, int have_prev, float prev_ev,
                         uint8_t* rgba8_out, uint32_t* histogram_out, float* ev_out);
+
+/* Bloom (no reference counterpart), opt-in: a multi-scale glare between the linear HDR image and the display transform.  A fraction
+ * `strength` of the light above `threshold` leaves its pixel and is spread by a kernel that is a mix of `levels` near-Gaussian scales;
+ * away from the image border light is neither created nor lost, so that a small emitter far above the key shows as a halo in proportion
+ * to its power where the tone curve alone clips it to white.  The result is a float4 plane of its own at the source's size; accum,
+ * frame and every *_frame plane keep their bits, and a context that never calls it keeps its footprint and its launches.
+ * Per texel, float32, no contraction, r g b alike, alpha copied.  I is the source, W x H:
+ *   1. C = I > 0 ? min(I, clamp) : 0  (NaN and negatives give 0, +inf gives clamp);  Y = 0.3 Cr + 0.6 Cg + 0.1 Cb;
+ *      t = Y > threshold ? (Y - threshold) / Y : 0;  P = C t   (a ramp, continuous at the threshold; threshold 0: P = C)
+ *   2. D_0 = P;  D_{k+1} is ceil(W_k / 2) x ceil(H_k / 2):  D_{k+1}(x, y) = sum_j sum_i w_j w_i D_k(cx(2x - 1 + i), cy(2y - 1 + j)),
+ *      i, j = 0 .. 3, w = (1, 3, 3, 1) / 8, cx / cy clamp to the level's edge; the four horizontal sums first, each
+ *      ((w0 a0 + w1 a1) + w2 a2) + w3 a3, then the same form down the column
+ *   3. g_k = spread^(k-1) / sum_{m=1..L} spread^(m-1) (in double, rounded to float once);  U_L = g_L D_L;  U_k = g_k D_k + up(U_{k+1});
+ *      B = up(U_1) at the source's size;  up(A)(x, y): px = x >> 1, nx = clamp(px + (x & 1 ? 1 : -1)), 0.75 A(px) + 0.25 A(nx)
+ *      horizontally on the rows py and ny, then the same vertically over those two
+ *   4. O = I + strength (B - P),  O_a = I_a.  What is above `clamp` stays where it was; a NaN stays in its channel of its pixel. */
+typedef struct spcbpt_bloom_params {
+    int32_t levels;       /* L, the scales of the pyramid: 1 .. 8 (a level never gets smaller than 1 x 1) */
+    float strength;       /* s, the share of the light above the threshold that is redistributed: [0, 1] */
+    float spread;         /* q, the weight of a level relative to the next finer one: (0, 4]; 1 weighs all levels alike */
+    float threshold;      /* T, the luminance below which a pixel gives nothing: >= 0 */
+    float clamp;          /* K, the most a channel may give: (0, 2^64] */
+} spcbpt_bloom_params;
+/* levels 5, strength 0.1, spread 1, threshold 0, clamp 65504 */
+int spcbpt_bloom_default_params(spcbpt_bloom_params* params);
+int spcbpt_bloom_params_struct_size(void);   /* sizeof(spcbpt_bloom_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+/* The stage on one of the context's linear images: source SPCBPT_DISPLAY_FILM, _DENOISED, _ROBUST or _HISTORY, as spcbpt_display takes
+ * them.  A link of the film-merge chain like spcbpt_display: it sees everything queued before it.  Writes only the context's bloom
+ * plane and its pyramid scratch (float4 per texel of the levels 1 .. L, about a third of the image).  The launches: a tiled down pass
+ * per fine level (level 0 with step 1 fused in), one workgroup that runs the coarse end of the pyramid down and back up in LDS, an up
+ * pass per fine level, the composite; one kernel-time span, "bloom".  SPCBPT_ERR_INVALID_ARG, with a text that contains `bloom`: a
+ * source that does not exist, a field outside its range above or not finite.  SPCBPT_ERR_STATE with spcbpt_display's texts: the source
+ * image does not exist, before spcbpt_resize, while a deferred frame is outstanding. */
+int spcbpt_bloom(spcbpt_ctx* ctx, int source, const spcbpt_bloom_params* params);
+/* The same stage on an image the caller holds (float4 per pixel, 1 .. 2^28 pixels): the film an N-GPU host has gathered, a PFM from
+ * disk.  The image is copied to a scratch buffer of the context before the call returns.  Needs no spcbpt_resize. */
+int spcbpt_bloom_image(spcbpt_ctx* ctx, const float* rgba, int width, int height, const spcbpt_bloom_params* params);
+/* The bloom plane the last spcbpt_bloom / spcbpt_bloom_image left: width x height float4 of that call's image size; every pointer may
+ * be NULL (ask for width / height first when the size is not known).  Waits like spcbpt_read_accum.  SPCBPT_ERR_STATE before the first
+ * bloom call since spcbpt_resize, which frees the plane and the pyramid (as spcbpt_destroy does). */
+int spcbpt_read_bloom(spcbpt_ctx* ctx, float* rgba, int* width, int* height);
+/* The same per-texel code over caller arrays on the host: no context and no GPU needed.  out_rgba: width x height float4, must not
+ * overlap rgba.  SPCBPT_ERR_INVALID_ARG as above, for a NULL pointer and for an image outside 1 .. 2^28 pixels. */
+int spcbpt_bloom_host(const float* rgba, int width, int height, const spcbpt_bloom_params* params, float* out_rgba);
 
 /* Adaptive sampling (no reference counterpart), opt-in: trace only the tiles of the film that are still above a target error.  A TILE
  * is an 8x8 pixel block of the whole film, numbered x-major: tile t covers x = (t % tiles_x) 8 ..., y = (t / tiles_x) 8 ... with
@@ -1076,7 +1122,7 @@ int spcbpt_lvc_import_wait(spcbpt_ctx* ctx);
 /* Kernel timing measured with HIP events on the context's stream: average
  * milliseconds per launch of `name` since the last reset, and launch count.  (The film merge behind a render launch is the span
  * "film_merge", the moments update in front of it "moments", the bucket update "buckets"; the display pass is "display_hist" and
- * "display".) */
+ * "display", the bloom stage "bloom".) */
 int spcbpt_kernel_time(spcbpt_ctx* ctx, const char* name, double* avg_ms, int* launches);
 int spcbpt_reset_kernel_time(spcbpt_ctx* ctx);
 int spcbpt_enable_kernel_timing(spcbpt_ctx* ctx, int enabled);

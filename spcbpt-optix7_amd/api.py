@@ -74,8 +74,12 @@ class DisplayParams(C.Structure):   # spcbpt_display_params
 TONE_OPS = {"film": 0, "reinhard": 1, "aces": 2, "linear": 3}
 DISPLAY_AUTO = 1
 DISPLAY_HISTOGRAM = 2
-DISPLAY_SOURCES = {"film": 0, "denoised": 1, "robust": 2, "history": 3}
+DISPLAY_SOURCES = {"film": 0, "denoised": 1, "robust": 2, "history": 3, "bloom": 4}   # "bloom": spcbpt_display only (the plane of Renderer.bloom)
 DISPLAY_COUNTERS = 258
+
+
+class BloomParams(C.Structure):   # spcbpt_bloom_params
+    _fields_ = [("levels", C.c_int32), ("strength", C.c_float), ("spread", C.c_float), ("threshold", C.c_float), ("clamp", C.c_float)]
 
 
 class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
@@ -604,6 +608,36 @@ def display_host(img, have_prev=False, prev_ev=0.0, **params):
     return out, hist, float(ev.value)
 
 
+def bloom_params(**fields):
+    """A spcbpt_bloom_params: the library's defaults (spcbpt_bloom_default_params), then any field by name (levels, strength, spread,
+    threshold, clamp)."""
+    lib = load_library()
+    p = BloomParams()
+    if lib.spcbpt_bloom_default_params(C.byref(p)) != 0:
+        raise SpcbptError("bloom_default_params failed")
+    names = {n for n, _ in BloomParams._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise SpcbptError(f"bloom_params: no field '{k}'")
+        setattr(p, k, v)
+    return p
+
+
+def bloom_host(img, **params):
+    """spcbpt_bloom_host: the bloom stage of an (h, w, 4) float32 image on the host, parameters as bloom_params takes them.  Returns the
+    (h, w, 4) float32 result.  The per-texel code the kernels run; no GPU needed."""
+    lib = load_library()
+    x = np.ascontiguousarray(img, dtype=np.float32)
+    if x.ndim != 3 or x.shape[-1] != 4:
+        raise SpcbptError("bloom_host: the image must be (h, w, 4)")
+    p = bloom_params(**params)
+    out = np.zeros(x.shape, np.float32)
+    rc = lib.spcbpt_bloom_host(_fp(x), x.shape[1], x.shape[0], C.byref(p), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"bloom_host failed ({rc})")
+    return out
+
+
 def film_error_host(accum, m2n):
     """spcbpt_film_error_host: {"pixels", "mean", "max"} of the relative standard error over the pixels with n >= 2, from (..., 4)
     float32 arrays as read_accum / read_film_moments give them.  The per-pixel function the kernel runs; no GPU needed."""
@@ -957,6 +991,12 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_read_display": [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32)],
         "spcbpt_display_reset": [vp],
         "spcbpt_display_host": [f32p, C.c_int64, C.POINTER(DisplayParams), i32, C.c_float, vp, vp, C.POINTER(C.c_float)],
+        "spcbpt_bloom_default_params": [C.POINTER(BloomParams)],
+        "spcbpt_bloom_params_struct_size": [],
+        "spcbpt_bloom": [vp, i32, C.POINTER(BloomParams)],
+        "spcbpt_bloom_image": [vp, f32p, i32, i32, C.POINTER(BloomParams)],
+        "spcbpt_read_bloom": [vp, vp, C.POINTER(i32), C.POINTER(i32)],
+        "spcbpt_bloom_host": [f32p, i32, i32, C.POINTER(BloomParams), f32p],
         "spcbpt_adaptive_params_struct_size": [], "spcbpt_adaptive_begin": [vp, u32], "spcbpt_adaptive_end": [vp],
         "spcbpt_adaptive_select": [vp, C.POINTER(AdaptiveParams), C.POINTER(i32)], "spcbpt_adaptive_set_tiles": [vp, vp, i32],
         "spcbpt_launch_adaptive": [vp, C.c_char_p], "spcbpt_read_adaptive": [vp, vp, vp, vp, i32, C.POINTER(i32)],
@@ -1039,6 +1079,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
     "spcbpt_display_default_params", "spcbpt_display_params_struct_size", "spcbpt_display", "spcbpt_display_image", "spcbpt_read_display", "spcbpt_display_reset", "spcbpt_display_host",
+    "spcbpt_bloom_default_params", "spcbpt_bloom_params_struct_size", "spcbpt_bloom", "spcbpt_bloom_image", "spcbpt_read_bloom", "spcbpt_bloom_host",
     "spcbpt_adaptive_params_struct_size", "spcbpt_adaptive_begin", "spcbpt_adaptive_end", "spcbpt_adaptive_select", "spcbpt_adaptive_set_tiles", "spcbpt_launch_adaptive",
     "spcbpt_read_adaptive", "spcbpt_get_adaptive_state", "spcbpt_adaptive_select_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
@@ -1277,6 +1318,31 @@ class Renderer:
     def display_reset(self):
         """spcbpt_display_reset: forget the previous EV (the next auto call jumps to its target)."""
         self._chk(self.lib.spcbpt_display_reset(self.h), "display_reset")
+
+    # ---- bloom (spcbpt_bloom*): a multi-scale glare ahead of the display transform -- a float4 plane of its own
+    def bloom(self, source="film", **params):
+        """spcbpt_bloom: one of the context's linear images ("film", "denoised", "robust", "history") with the share `strength` of its
+        light above `threshold` spread over `levels` scales, into the bloom plane.  Parameters as bloom_params takes them.  Read with
+        read_bloom(); show with display("bloom", ...)."""
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        p = bloom_params(**params)
+        self._chk(self.lib.spcbpt_bloom(self.h, src, C.byref(p)), "bloom")
+
+    def bloom_image(self, img, **params):
+        """spcbpt_bloom_image: the same stage on an (h, w, 4) float32 image of the caller's, any size."""
+        x = np.ascontiguousarray(img, dtype=np.float32)
+        if x.ndim != 3 or x.shape[-1] != 4:
+            raise SpcbptError("bloom_image: the image must be (h, w, 4)")
+        p = bloom_params(**params)
+        self._chk(self.lib.spcbpt_bloom_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "bloom_image")
+
+    def read_bloom(self):
+        """(h, w, 4) float32: the plane the last bloom() / bloom_image() wrote, at that call's image size."""
+        w, h = C.c_int32(), C.c_int32()
+        self._chk(self.lib.spcbpt_read_bloom(self.h, None, C.byref(w), C.byref(h)), "read_bloom")
+        out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_bloom(self.h, out.ctypes.data, None, None), "read_bloom")
+        return out
 
     # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major
     def adaptive_begin(self, frames: int):

@@ -392,6 +392,19 @@ struct Context {
     int display_run(const float* src, int width, int height, const spcbpt_display_params& p);   // the launches, on `rstream` inside a chain link
     int display_reset();
     void free_display();
+    // Bloom (ctx_bloom.hip; spcbpt_bloom / spcbpt_bloom_image, opt-in): a float4 plane of its own at the size of the image it was made
+    // from, the pyramid scratch (float4 per texel of the levels 1 .. L: about a third of the image) and, for spcbpt_bloom_image, a scratch
+    // copy of the caller's image.  Allocated at the first call, grow-only; spcbpt_resize frees all three.  A context that does not ask
+    // keeps its footprint, its launches and every plane's bits.
+    DevBuf<float> d_bloom, d_bloom_pyr, d_bloom_src;
+    struct Bloom {
+        bool have = false;         // a bloom plane since the last resize
+        int width = 0, height = 0; // ... its size
+    } bloom_last;
+    int bloom(int source, const spcbpt_bloom_params& p);
+    int bloom_image(const float* rgba, int width, int height, const spcbpt_bloom_params& p);
+    int bloom_run(const float* src, int width, int height, const spcbpt_bloom_params& p);   // the launches, on `rstream` inside a chain link
+    void free_bloom();
     // Adaptive sampling (ctx_adaptive.hip; spcbpt_adaptive_*): between adaptive_begin and adaptive_end / resize / clear_accum the film is
     // merged tile by tile, every 8x8 tile at a sample index of its own.  Per tile of the film a count (uint32) and an error (float, with
     // the number of pixels it is the mean of), a tile list (uint32, strictly ascending) and its length: 16 B per tile and 4 B, allocated

@@ -23,7 +23,10 @@
 // the run produced -- the robust image, else the denoised one, else the film -- at a manual EV (default 0) or at the EV measured from
 // that image's luminance histogram (key K, default 0.18), through the tone operator (default film); writes <out>_display.ppm next to
 // the usual files, which stay as they are, and prints the EV used.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--out prefix]
+// --bloom S [--bloom-levels N] [--bloom-threshold T]: that image goes through spcbpt_bloom first (strength S in [0, 1], N = 1 .. 8 levels,
+// default 5, luminance threshold T, default 0) and the bloom plane is what <out>_display.ppm shows; --bloom alone implies the display
+// pass with its defaults.  <out>.pfm and <out>.ppm keep their bytes.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -64,7 +67,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -80,6 +83,9 @@ int main(int argc, char** argv) {
     bool display = false;         // any of --exposure / --auto-exposure / --tone / --key
     spcbpt_display_params disp;
     spcbpt_display_default_params(&disp);
+    bool bloom = false;           // --bloom S: the shown image goes through spcbpt_bloom first
+    spcbpt_bloom_params blm;
+    spcbpt_bloom_default_params(&blm);
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -112,6 +118,9 @@ int main(int argc, char** argv) {
             else { fprintf(stderr, "--tone takes film, reinhard, aces or linear\n"); return 1; }
             display = true;
         }
+        else if (a == "--bloom" && i + 1 < argc) { blm.strength = (float)atof(argv[++i]); bloom = true; display = true; }
+        else if (a == "--bloom-levels" && i + 1 < argc) blm.levels = atoi(argv[++i]);
+        else if (a == "--bloom-threshold" && i + 1 < argc) blm.threshold = (float)atof(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -237,7 +246,8 @@ int main(int argc, char** argv) {
     }
     if (robust) CHECK(ctx, spcbpt_robust_resolve(ctx, robust_strength));
     const int display_source = robust ? SPCBPT_DISPLAY_ROBUST : (denoise ? SPCBPT_DISPLAY_DENOISED : SPCBPT_DISPLAY_FILM);
-    if (display) CHECK(ctx, spcbpt_display(ctx, display_source, &disp));
+    if (bloom) CHECK(ctx, spcbpt_bloom(ctx, display_source, &blm));
+    if (display) CHECK(ctx, spcbpt_display(ctx, bloom ? SPCBPT_DISPLAY_BLOOM : display_source, &disp));
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
@@ -289,6 +299,7 @@ int main(int argc, char** argv) {
         static const char* const tones[] = {"film", "reinhard", "aces", "linear"};
         printf("wrote %s_display.ppm (%s, tone %s, %s EV %.9g)\n", out.c_str(), robust ? "the robust image" : (denoise ? "the denoised image" : "the film"), tones[disp.op],
                (disp.flags & SPCBPT_DISPLAY_AUTO) ? "auto" : "manual", ev);
+        if (bloom) printf("  through spcbpt_bloom: strength %g, %d levels, threshold %g\n", blm.strength, blm.levels, blm.threshold);
     }
     if (features) {
         std::vector<float> normal_depth((size_t)width * height * 4);
