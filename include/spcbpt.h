@@ -622,7 +622,8 @@ enum { SPCBPT_TONE_FILM = 0, SPCBPT_TONE_REINHARD = 1, SPCBPT_TONE_ACES = 2, SPC
 enum { SPCBPT_DISPLAY_AUTO = 1,          /* EV from the image's histogram (`ev` is ignored) */
        SPCBPT_DISPLAY_HISTOGRAM = 2 };   /* compute the histogram under manual exposure too, for spcbpt_read_display */
 enum { SPCBPT_DISPLAY_FILM = 0, SPCBPT_DISPLAY_DENOISED = 1, SPCBPT_DISPLAY_ROBUST = 2, SPCBPT_DISPLAY_HISTORY = 3,
-       SPCBPT_DISPLAY_BLOOM = 4 };       /* spcbpt_display only: the bloom plane (spcbpt_bloom, below) */
+       SPCBPT_DISPLAY_BLOOM = 4,         /* spcbpt_display and spcbpt_local_tone only: the bloom plane (spcbpt_bloom, below) */
+       SPCBPT_DISPLAY_LOCAL = 5 };       /* spcbpt_display only: the local tone plane (spcbpt_local_tone, below) */
 typedef struct spcbpt_display_params {
     int32_t op;                           /* SPCBPT_TONE_* */
     uint32_t flags;                       /* SPCBPT_DISPLAY_AUTO | SPCBPT_DISPLAY_HISTOGRAM */
@@ -637,8 +638,9 @@ typedef struct spcbpt_display_params {
 int spcbpt_display_default_params(spcbpt_display_params* params);
 int spcbpt_display_params_struct_size(void);   /* sizeof(spcbpt_display_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
 /* The pass on one of the context's linear images: source SPCBPT_DISPLAY_FILM (accum), _DENOISED (the latest output of spcbpt_denoise /
- * spcbpt_denoise_variance / spcbpt_history_denoise), _ROBUST (spcbpt_robust_resolve), _HISTORY (spcbpt_history_resolve) or _BLOOM (the
- * plane spcbpt_bloom / spcbpt_bloom_image left, at that plane's own size; SPCBPT_ERR_STATE naming spcbpt_bloom without one).  A link of
+ * spcbpt_denoise_variance / spcbpt_history_denoise), _ROBUST (spcbpt_robust_resolve), _HISTORY (spcbpt_history_resolve), _BLOOM (the
+ * plane spcbpt_bloom / spcbpt_bloom_image left, at that plane's own size; SPCBPT_ERR_STATE naming spcbpt_bloom without one) or _LOCAL
+ * (the plane spcbpt_local_tone / spcbpt_local_tone_image left, likewise; SPCBPT_ERR_STATE naming spcbpt_local_tone).  A link of
  * the film-merge chain like spcbpt_robust_resolve: it sees everything queued before it.  Manual exposure is one launch; auto is a memset
  * of the counters, the histogram, the exposure kernel and the tone map on one stream.  Writes only its own plane and record.
  * SPCBPT_ERR_INVALID_ARG: a source or op that does not exist, unknown flag bits, fractions outside [0, 1) or summing to >= 1,
@@ -708,6 +710,67 @@ int spcbpt_read_bloom(spcbpt_ctx* ctx, float* rgba, int* width, int* height);
 /* The same per-texel code over caller arrays on the host: no context and no GPU needed.  out_rgba: width x height float4, must not
  * overlap rgba.  SPCBPT_ERR_INVALID_ARG as above, for a NULL pointer and for an image outside 1 .. 2^28 pixels. */
 int spcbpt_bloom_host(const float* rgba, int width, int height, const spcbpt_bloom_params* params, float* out_rgba);
+
+/* Local tone mapping (no reference counterpart), opt-in: a base / detail decomposition of log-luminance through a bilateral grid
+ * (Chen, Paris and Durand 2007; Durand and Dorsey 2002) between the linear HDR image -- or the bloom plane -- and the display
+ * transform.  The large-scale luminance range of the image is compressed about `anchor`, local contrast is kept, and because the grid
+ * separates pixels by luminance as well as by position a strong edge gets no halo: an interior lit by a small bright emitter keeps
+ * both the lamp's wall and the far corner inside one exposure.  The result is a float4 plane of its own at the source's size; every
+ * other plane keeps its bits, and a context that never calls it keeps its footprint and its launches.
+ * Float32 per pixel and per grid node, no contraction; only + - x /, compares, int <-> float conversions and bit-pattern moves are on
+ * the path, so the device plane equals spcbpt_local_tone_host bit for bit.  I is the source, W x H, s = cell, rho = range:
+ *   1. Y = 0.3 r + 0.6 g + 0.1 b.  A pixel TAKES PART iff Y > 0 && Y < +inf (NaN, zero, negatives and infinities do not).  For those
+ *      Yc = min(max(Y, 2^-16), 2^16) and L = lt_log2(Yc) in [-16, 16]:  lt_log2 = e + P(m - 1), e and m in [1, 2) cut from the bit
+ *      pattern, P(t) = t + t (0.44183588 + t (-0.7083722 + t (0.41355506 + t (-0.19126251 + t 0.04424374)))), P(0) = 0 exactly.
+ *      Its inverse lt_exp2(g): g clamped to [-32, 32], i = floor(g), f = g - i, Q(f) times the float with the bit pattern
+ *      (i + 127) << 23, Q(f) = 1 + f (0.6930049 + f (0.24153961 + f (0.051766057 + f 0.013689456))), lt_exp2(0) == 1 exactly.
+ *      |lt_log2 - log2| <= 1.8e-5 stops, |lt_exp2 / exp2 - 1| <= 4.6e-6 (the condition is 2^-13 for both); both are non-decreasing.
+ *   2. The grid: GX = (W - 1) / s + 2, GY = (H - 1) / s + 2 (integer division), NZ = (int)(32 / rho) + 2 (the quotient in float32),
+ *      two channels A, B per node; a pixel's bin coordinate is z = (L + 16) / rho.  More than 2^25 nodes: SPCBPT_ERR_INVALID_ARG.
+ *      Node (gx, gy, gz) gathers the pixels that take part with |x - gx s| < s and |y - gy s| < s under the tents
+ *      wx = (float)(s - |x - gx s|) / (float)s, wy likewise, wz = 1 - |z - (float)gz| where that is > 0, else 0.  The order of the sums
+ *      is part of the definition: row sums, x ascending, a_j = sum (wx wz) L and b_j = sum (wx wz); then, rows ascending,
+ *      A = sum wy_j a_j and B = sum wy_j b_j; each a plain left-to-right float32 sum from 0.  A gather, no atomics: deterministic.
+ *   3. Blur, `blur` times: along x over the whole grid, then y, then z, both channels,
+ *      out(i) = (0.25 v(i - 1) + 0.5 v(i)) + 0.25 v(i + 1), indices clamped to the grid.
+ *   4. Slice, for a pixel that takes part: ix = x / s, tx = (float)(x - ix s) / (float)s, the same in y; iz = min((int)z, NZ - 2),
+ *      tz = z - (float)iz; lerp(a, b, t) = a + t (b - a).  A and B separately: along z in each of the four columns, then along x in the
+ *      rows iy and iy + 1, then along y.  base = A / B if B > 0, else L.
+ *   5. g = (compress - 1)(base - La) + (detail - 1)(L - base), La = log2(anchor) taken in double and rounded to float once;
+ *      O_rgb = I_rgb lt_exp2(g), O_a = I_a.  A pixel that takes no part keeps its four floats bit for bit; with compress = detail = 1
+ *      the whole plane is the source bit for bit. */
+typedef struct spcbpt_local_tone_params {
+    int32_t cell;         /* s, pixels per grid cell: 4 .. 64 */
+    float range;          /* rho, stops per grid bin: [0.5, 8] */
+    int32_t blur;         /* grid blur passes: 0 .. 4 */
+    float compress;       /* c, the slope of the base layer: (0, 2]; 1 leaves the large-scale range as it is */
+    float detail;         /* d, the slope of the detail layer: [0, 4]; 1 leaves local contrast as it is */
+    float anchor;         /* the luminance whose base stays put: > 0 */
+} spcbpt_local_tone_params;
+/* cell 16, range 1, blur 1, compress 0.5, detail 1, anchor 0.18 */
+int spcbpt_local_tone_default_params(spcbpt_local_tone_params* params);
+int spcbpt_local_tone_params_struct_size(void);   /* sizeof(spcbpt_local_tone_params) as the library was compiled (spcbpt_abi_struct_sizes keeps its 13 entries) */
+/* The stage on one of the context's linear images: source SPCBPT_DISPLAY_FILM, _DENOISED, _ROBUST or _HISTORY as spcbpt_display takes
+ * them, or _BLOOM: glare first, then the local operator.  The local plane itself is no source, of this stage or of spcbpt_bloom.  A
+ * link of the film-merge chain like spcbpt_bloom: it sees everything queued before it.  Writes only the context's local tone plane and
+ * its two grid buffers (two floats per node each).  The launches: the gather (one workgroup per node column), one launch per
+ * blur pass (its three axes together), the slice with the gain; one kernel-time span, "local_tone".  SPCBPT_ERR_INVALID_ARG, with a text that contains
+ * `local_tone`: a source that does not exist, a field outside its range above or not finite, a grid of more than 2^25 nodes.
+ * SPCBPT_ERR_STATE with spcbpt_display's texts: the source image does not exist (naming spcbpt_bloom for _BLOOM), before
+ * spcbpt_resize, while a deferred frame is outstanding. */
+int spcbpt_local_tone(spcbpt_ctx* ctx, int source, const spcbpt_local_tone_params* params);
+/* The same stage on an image the caller holds (float4 per pixel, 1 .. 2^28 pixels).  The image is copied to a scratch buffer of the
+ * context before the call returns.  Needs no spcbpt_resize. */
+int spcbpt_local_tone_image(spcbpt_ctx* ctx, const float* rgba, int width, int height, const spcbpt_local_tone_params* params);
+/* The plane the last spcbpt_local_tone / spcbpt_local_tone_image left: width x height float4 of that call's image size; every pointer
+ * may be NULL.  Waits like spcbpt_read_accum.  SPCBPT_ERR_STATE before the first call since spcbpt_resize, which frees the plane and
+ * the grid buffers (as spcbpt_destroy does). */
+int spcbpt_read_local_tone(spcbpt_ctx* ctx, float* rgba, int* width, int* height);
+/* The same per-pixel and per-node code over caller arrays on the host: no context and no GPU needed.  out_rgba: width x height float4,
+ * must not overlap rgba.  SPCBPT_ERR_INVALID_ARG as above, for a NULL pointer and for an image outside 1 .. 2^28 pixels. */
+int spcbpt_local_tone_host(const float* rgba, int width, int height, const spcbpt_local_tone_params* params, float* out_rgba);
+/* For the tests: lt_log2 (which = 0) or lt_exp2 (which = 1) of step 1 over n floats. */
+int spcbpt_local_tone_math_host(const float* in, int64_t n, int which, float* out);
 
 /* Adaptive sampling (no reference counterpart), opt-in: trace only the tiles of the film that are still above a target error.  A TILE
  * is an 8x8 pixel block of the whole film, numbered x-major: tile t covers x = (t % tiles_x) 8 ..., y = (t / tiles_x) 8 ... with
@@ -1122,7 +1185,7 @@ int spcbpt_lvc_import_wait(spcbpt_ctx* ctx);
 /* Kernel timing measured with HIP events on the context's stream: average
  * milliseconds per launch of `name` since the last reset, and launch count.  (The film merge behind a render launch is the span
  * "film_merge", the moments update in front of it "moments", the bucket update "buckets"; the display pass is "display_hist" and
- * "display", the bloom stage "bloom".) */
+ * "display", the bloom stage "bloom", the local tone stage "local_tone".) */
 int spcbpt_kernel_time(spcbpt_ctx* ctx, const char* name, double* avg_ms, int* launches);
 int spcbpt_reset_kernel_time(spcbpt_ctx* ctx);
 int spcbpt_enable_kernel_timing(spcbpt_ctx* ctx, int enabled);

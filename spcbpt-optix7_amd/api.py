@@ -74,12 +74,16 @@ class DisplayParams(C.Structure):   # spcbpt_display_params
 TONE_OPS = {"film": 0, "reinhard": 1, "aces": 2, "linear": 3}
 DISPLAY_AUTO = 1
 DISPLAY_HISTOGRAM = 2
-DISPLAY_SOURCES = {"film": 0, "denoised": 1, "robust": 2, "history": 3, "bloom": 4}   # "bloom": spcbpt_display only (the plane of Renderer.bloom)
+DISPLAY_SOURCES = {"film": 0, "denoised": 1, "robust": 2, "history": 3, "bloom": 4, "local": 5}   # "bloom": spcbpt_display and spcbpt_local_tone only (the plane of Renderer.bloom); "local": spcbpt_display only (the plane of Renderer.local_tone)
 DISPLAY_COUNTERS = 258
 
 
 class BloomParams(C.Structure):   # spcbpt_bloom_params
     _fields_ = [("levels", C.c_int32), ("strength", C.c_float), ("spread", C.c_float), ("threshold", C.c_float), ("clamp", C.c_float)]
+
+
+class LocalToneParams(C.Structure):   # spcbpt_local_tone_params
+    _fields_ = [("cell", C.c_int32), ("range", C.c_float), ("blur", C.c_int32), ("compress", C.c_float), ("detail", C.c_float), ("anchor", C.c_float)]
 
 
 class FilmErrorStats(C.Structure):   # spcbpt_film_error_stats
@@ -638,6 +642,47 @@ def bloom_host(img, **params):
     return out
 
 
+def local_tone_params(**fields):
+    """A spcbpt_local_tone_params: the library's defaults (spcbpt_local_tone_default_params), then any field by name (cell, range, blur,
+    compress, detail, anchor)."""
+    lib = load_library()
+    p = LocalToneParams()
+    if lib.spcbpt_local_tone_default_params(C.byref(p)) != 0:
+        raise SpcbptError("local_tone_default_params failed")
+    names = {n for n, _ in LocalToneParams._fields_}
+    for k, v in fields.items():
+        if k not in names:
+            raise SpcbptError(f"local_tone_params: no field '{k}'")
+        setattr(p, k, v)
+    return p
+
+
+def local_tone_host(img, **params):
+    """spcbpt_local_tone_host: the local tone stage of an (h, w, 4) float32 image on the host, parameters as local_tone_params takes
+    them.  Returns the (h, w, 4) float32 result.  The per-pixel and per-node code the kernels run; no GPU needed."""
+    lib = load_library()
+    x = np.ascontiguousarray(img, dtype=np.float32)
+    if x.ndim != 3 or x.shape[-1] != 4:
+        raise SpcbptError("local_tone_host: the image must be (h, w, 4)")
+    p = local_tone_params(**params)
+    out = np.zeros(x.shape, np.float32)
+    rc = lib.spcbpt_local_tone_host(_fp(x), x.shape[1], x.shape[0], C.byref(p), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"local_tone_host failed ({rc})")
+    return out
+
+
+def local_tone_math_host(values, which):
+    """spcbpt_local_tone_math_host (for the tests): lt_log2 (which = 0) or lt_exp2 (which = 1) of the stage over a float32 array."""
+    lib = load_library()
+    x = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.zeros(x.shape, np.float32)
+    rc = lib.spcbpt_local_tone_math_host(_fp(x), x.size, int(which), _fp(out))
+    if rc != 0:
+        raise SpcbptError(f"local_tone_math_host failed ({rc})")
+    return out
+
+
 def film_error_host(accum, m2n):
     """spcbpt_film_error_host: {"pixels", "mean", "max"} of the relative standard error over the pixels with n >= 2, from (..., 4)
     float32 arrays as read_accum / read_film_moments give them.  The per-pixel function the kernel runs; no GPU needed."""
@@ -997,6 +1042,13 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_bloom_image": [vp, f32p, i32, i32, C.POINTER(BloomParams)],
         "spcbpt_read_bloom": [vp, vp, C.POINTER(i32), C.POINTER(i32)],
         "spcbpt_bloom_host": [f32p, i32, i32, C.POINTER(BloomParams), f32p],
+        "spcbpt_local_tone_default_params": [C.POINTER(LocalToneParams)],
+        "spcbpt_local_tone_params_struct_size": [],
+        "spcbpt_local_tone": [vp, i32, C.POINTER(LocalToneParams)],
+        "spcbpt_local_tone_image": [vp, f32p, i32, i32, C.POINTER(LocalToneParams)],
+        "spcbpt_read_local_tone": [vp, vp, C.POINTER(i32), C.POINTER(i32)],
+        "spcbpt_local_tone_host": [f32p, i32, i32, C.POINTER(LocalToneParams), f32p],
+        "spcbpt_local_tone_math_host": [f32p, C.c_int64, i32, f32p],
         "spcbpt_adaptive_params_struct_size": [], "spcbpt_adaptive_begin": [vp, u32], "spcbpt_adaptive_end": [vp],
         "spcbpt_adaptive_select": [vp, C.POINTER(AdaptiveParams), C.POINTER(i32)], "spcbpt_adaptive_set_tiles": [vp, vp, i32],
         "spcbpt_launch_adaptive": [vp, C.c_char_p], "spcbpt_read_adaptive": [vp, vp, vp, vp, i32, C.POINTER(i32)],
@@ -1080,6 +1132,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
     "spcbpt_display_default_params", "spcbpt_display_params_struct_size", "spcbpt_display", "spcbpt_display_image", "spcbpt_read_display", "spcbpt_display_reset", "spcbpt_display_host",
     "spcbpt_bloom_default_params", "spcbpt_bloom_params_struct_size", "spcbpt_bloom", "spcbpt_bloom_image", "spcbpt_read_bloom", "spcbpt_bloom_host",
+    "spcbpt_local_tone_default_params", "spcbpt_local_tone_params_struct_size", "spcbpt_local_tone", "spcbpt_local_tone_image", "spcbpt_read_local_tone", "spcbpt_local_tone_host", "spcbpt_local_tone_math_host",
     "spcbpt_adaptive_params_struct_size", "spcbpt_adaptive_begin", "spcbpt_adaptive_end", "spcbpt_adaptive_select", "spcbpt_adaptive_set_tiles", "spcbpt_launch_adaptive",
     "spcbpt_read_adaptive", "spcbpt_get_adaptive_state", "spcbpt_adaptive_select_host",
     "spcbpt_history_capture", "spcbpt_history_reproject", "spcbpt_history_resolve", "spcbpt_history_reset", "spcbpt_read_history", "spcbpt_reproject_params_struct_size",
@@ -1342,6 +1395,31 @@ class Renderer:
         self._chk(self.lib.spcbpt_read_bloom(self.h, None, C.byref(w), C.byref(h)), "read_bloom")
         out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
         self._chk(self.lib.spcbpt_read_bloom(self.h, out.ctypes.data, None, None), "read_bloom")
+        return out
+
+    # ---- local tone mapping (spcbpt_local_tone*): base / detail through a bilateral grid -- a float4 plane of its own
+    def local_tone(self, source="film", **params):
+        """spcbpt_local_tone: one of the context's linear images ("film", "denoised", "robust", "history") or the bloom plane ("bloom")
+        with its large-scale luminance range compressed by `compress` about `anchor` and its local contrast scaled by `detail`, into the
+        local tone plane.  Parameters as local_tone_params takes them.  Read with read_local_tone(); show with display("local", ...)."""
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        p = local_tone_params(**params)
+        self._chk(self.lib.spcbpt_local_tone(self.h, src, C.byref(p)), "local_tone")
+
+    def local_tone_image(self, img, **params):
+        """spcbpt_local_tone_image: the same stage on an (h, w, 4) float32 image of the caller's, any size."""
+        x = np.ascontiguousarray(img, dtype=np.float32)
+        if x.ndim != 3 or x.shape[-1] != 4:
+            raise SpcbptError("local_tone_image: the image must be (h, w, 4)")
+        p = local_tone_params(**params)
+        self._chk(self.lib.spcbpt_local_tone_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "local_tone_image")
+
+    def read_local_tone(self):
+        """(h, w, 4) float32: the plane the last local_tone() / local_tone_image() wrote, at that call's image size."""
+        w, h = C.c_int32(), C.c_int32()
+        self._chk(self.lib.spcbpt_read_local_tone(self.h, None, C.byref(w), C.byref(h)), "read_local_tone")
+        out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_local_tone(self.h, out.ctypes.data, None, None), "read_local_tone")
         return out
 
     # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major

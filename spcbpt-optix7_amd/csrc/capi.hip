@@ -371,6 +371,7 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     c->free_buckets();            // ... and the bucket film with its resolved image (K stays)
     c->free_display();            // ... and the display plane with its record: the previous EV is forgotten
     c->free_bloom();              // ... and the bloom plane with its pyramid
+    c->free_local_tone();         // ... and the local tone plane with its grid buffers
     c->free_history();            // ... and the history, its prior and the resolved image
     c->splat_records_rk = -1;     // the records of an ordered "lt" launch belong to the old film (their buffers follow the cache capacity and stay)
     HIP_TRY(c, c->d_accum.reserve((size_t)w * h * 4));

@@ -8,6 +8,7 @@
 //   ctx_buckets.hip   Context + extern "C": the bucket film and its median-of-means resolve
 //   ctx_display.hip   Context + extern "C": the display transform -- exposure, histogram auto-exposure, tone operators
 //   ctx_bloom.hip     Context + extern "C": the bloom stage -- a multi-scale glare ahead of the display transform
+//   ctx_local_tone.hip Context + extern "C": the local tone stage -- base / detail through a bilateral grid, ahead of the display transform
 //   ctx_history.hip   Context + extern "C": history capture, reprojection into the current view, resolve
 //   ctx_adaptive.hip  Context + extern "C": adaptive sampling -- tile counts, tile selection, the list-fed eye launch and its merge
 //   capi.hip          extern "C": create / destroy, state, launches by name

@@ -405,6 +405,20 @@ struct Context {
     int bloom_image(const float* rgba, int width, int height, const spcbpt_bloom_params& p);
     int bloom_run(const float* src, int width, int height, const spcbpt_bloom_params& p);   // the launches, on `rstream` inside a chain link
     void free_bloom();
+    // Local tone mapping (ctx_local_tone.hip; spcbpt_local_tone / spcbpt_local_tone_image, opt-in): a float4 plane of its own at the size
+    // of the image it was made from, the two grid buffers the gather and the blur passes go back and forth between (two floats per node,
+    // (W / cell + 2)(H / cell + 2)(32 / range + 2) nodes: 2.3 MB each at 1920 x 1080 with the defaults) and, for spcbpt_local_tone_image,
+    // a scratch copy of the caller's image.  Allocated at the first call, grow-only; spcbpt_resize frees all four.  A context that does
+    // not ask keeps its footprint, its launches and every plane's bits.
+    DevBuf<float> d_local, d_local_grid[2], d_local_src;
+    struct LocalTone {
+        bool have = false;         // a local tone plane since the last resize
+        int width = 0, height = 0; // ... its size
+    } local_last;
+    int local_tone(int source, const spcbpt_local_tone_params& p);
+    int local_tone_image(const float* rgba, int width, int height, const spcbpt_local_tone_params& p);
+    int local_tone_run(const float* src, int width, int height, const spcbpt_local_tone_params& p);   // the launches, on `rstream` inside a chain link
+    void free_local_tone();
     // Adaptive sampling (ctx_adaptive.hip; spcbpt_adaptive_*): between adaptive_begin and adaptive_end / resize / clear_accum the film is
     // merged tile by tile, every 8x8 tile at a sample index of its own.  Per tile of the film a count (uint32) and an error (float, with
     // the number of pixels it is the mean of), a tile list (uint32, strictly ascending) and its length: 16 B per tile and 4 B, allocated

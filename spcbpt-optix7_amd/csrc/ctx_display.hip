@@ -53,13 +53,20 @@ int Context::display_run(const float* src, int width, int height, const spcbpt_d
 // it, and nothing queued later rewrites its source under it.  Writes its own plane and record only.
 int Context::display(int source, const spcbpt_display_params& p) {
     if (const char* bad = display_check(p)) { error = bad; return SPCBPT_ERR_INVALID_ARG; }
-    if (source < SPCBPT_DISPLAY_FILM || source > SPCBPT_DISPLAY_BLOOM) { error = "display: source must be 0 (film), 1 (denoised), 2 (robust), 3 (history) or 4 (bloom)"; return SPCBPT_ERR_INVALID_ARG; }
+    if (source < SPCBPT_DISPLAY_FILM || source > SPCBPT_DISPLAY_LOCAL) { error = "display: source must be 0 (film), 1 (denoised), 2 (robust), 3 (history), 4 (bloom) or 5 (local)"; return SPCBPT_ERR_INVALID_ARG; }
     if (deferred.active) { error = "display: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (source == SPCBPT_DISPLAY_BLOOM) {   // the bloom plane, at the size of the image it was made from (spcbpt_bloom_image needs no film)
         if (!bloom_last.have) { error = "display: no bloom plane: spcbpt_bloom / spcbpt_bloom_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
         next_render_stream();
         if (int rc = chain_wait()) return rc;
         if (int rc = display_run(d_bloom, bloom_last.width, bloom_last.height, p)) return rc;
+        return chain_end();
+    }
+    if (source == SPCBPT_DISPLAY_LOCAL) {   // the local tone plane, likewise at its own size
+        if (!local_last.have) { error = "display: no local tone plane: spcbpt_local_tone / spcbpt_local_tone_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+        next_render_stream();
+        if (int rc = chain_wait()) return rc;
+        if (int rc = display_run(d_local, local_last.width, local_last.height, p)) return rc;
         return chain_end();
     }
     if (!d_accum) { error = "display before spcbpt_resize"; return SPCBPT_ERR_STATE; }

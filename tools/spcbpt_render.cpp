@@ -26,7 +26,10 @@
 // --bloom S [--bloom-levels N] [--bloom-threshold T]: that image goes through spcbpt_bloom first (strength S in [0, 1], N = 1 .. 8 levels,
 // default 5, luminance threshold T, default 0) and the bloom plane is what <out>_display.ppm shows; --bloom alone implies the display
 // pass with its defaults.  <out>.pfm and <out>.ppm keep their bytes.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--out prefix]
+// --local-tone C [--local-detail D] [--local-cell S] [--local-range R]: that image -- after --bloom, if given -- goes through
+// spcbpt_local_tone (compress C in (0, 2], detail D, default 1, S = 4 .. 64 pixels per grid cell, default 16, R stops per bin, default 1)
+// and the local tone plane is what <out>_display.ppm shows; --local-tone alone implies the display pass with its defaults.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -67,7 +70,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -86,6 +89,9 @@ int main(int argc, char** argv) {
     bool bloom = false;           // --bloom S: the shown image goes through spcbpt_bloom first
     spcbpt_bloom_params blm;
     spcbpt_bloom_default_params(&blm);
+    bool local_tone = false;      // --local-tone C: the shown image goes through spcbpt_local_tone (after spcbpt_bloom, if both)
+    spcbpt_local_tone_params ltp;
+    spcbpt_local_tone_default_params(&ltp);
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -121,6 +127,10 @@ int main(int argc, char** argv) {
         else if (a == "--bloom" && i + 1 < argc) { blm.strength = (float)atof(argv[++i]); bloom = true; display = true; }
         else if (a == "--bloom-levels" && i + 1 < argc) blm.levels = atoi(argv[++i]);
         else if (a == "--bloom-threshold" && i + 1 < argc) blm.threshold = (float)atof(argv[++i]);
+        else if (a == "--local-tone" && i + 1 < argc) { ltp.compress = (float)atof(argv[++i]); local_tone = true; display = true; }
+        else if (a == "--local-detail" && i + 1 < argc) ltp.detail = (float)atof(argv[++i]);
+        else if (a == "--local-cell" && i + 1 < argc) ltp.cell = atoi(argv[++i]);
+        else if (a == "--local-range" && i + 1 < argc) ltp.range = (float)atof(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -247,7 +257,8 @@ int main(int argc, char** argv) {
     if (robust) CHECK(ctx, spcbpt_robust_resolve(ctx, robust_strength));
     const int display_source = robust ? SPCBPT_DISPLAY_ROBUST : (denoise ? SPCBPT_DISPLAY_DENOISED : SPCBPT_DISPLAY_FILM);
     if (bloom) CHECK(ctx, spcbpt_bloom(ctx, display_source, &blm));
-    if (display) CHECK(ctx, spcbpt_display(ctx, bloom ? SPCBPT_DISPLAY_BLOOM : display_source, &disp));
+    if (local_tone) CHECK(ctx, spcbpt_local_tone(ctx, bloom ? SPCBPT_DISPLAY_BLOOM : display_source, &ltp));
+    if (display) CHECK(ctx, spcbpt_display(ctx, local_tone ? SPCBPT_DISPLAY_LOCAL : (bloom ? SPCBPT_DISPLAY_BLOOM : display_source), &disp));
     CHECK(ctx, spcbpt_sync(ctx));
     auto t2 = std::chrono::steady_clock::now();
     const double sec = std::chrono::duration<double>(t2 - t1).count();
@@ -300,6 +311,7 @@ int main(int argc, char** argv) {
         printf("wrote %s_display.ppm (%s, tone %s, %s EV %.9g)\n", out.c_str(), robust ? "the robust image" : (denoise ? "the denoised image" : "the film"), tones[disp.op],
                (disp.flags & SPCBPT_DISPLAY_AUTO) ? "auto" : "manual", ev);
         if (bloom) printf("  through spcbpt_bloom: strength %g, %d levels, threshold %g\n", blm.strength, blm.levels, blm.threshold);
+        if (local_tone) printf("  through spcbpt_local_tone: compress %g, detail %g, cell %d, range %g\n", ltp.compress, ltp.detail, ltp.cell, ltp.range);
     }
     if (features) {
         std::vector<float> normal_depth((size_t)width * height * 4);
