@@ -345,6 +345,47 @@ int spcbpt_camera_splat(const float eye[3], const float U[3], const float V[3], 
                         int width, int height, const float point[3],
                         float* dx, float* dy, int* px, int* py, float* weight);
 
+/* Thin-lens camera: a finite aperture, i.e. depth of field.  Off by default (radius 0 = the pinhole: every launch then runs the
+ * kernels it always ran and every film keeps its bits; `focus` is ignored).
+ *   radius >= 0   lens radius in world units; the lens is the disc around `eye` in the plane spanned by U and V
+ *   focus  > 0    depth of the plane in focus, in units of W (for spcbpt_set_camera_lookat: 1 = the plane through `lookat`)
+ * A pixel sample (x + jx, y + jy) has dx, dy as for the pinhole and the focus point F = eye + focus (dx U + dy V + W); its lens point
+ * is O = eye + radius (a U / |U| + b V / |V|), (a, b) the concentric map of two uniform numbers onto the unit disc; the ray is
+ * (O, normalize(F - O)) with weight 1, so a pixel is the mean over its footprint and over the lens of the radiance along that ray (no
+ * cos^4 factor: with radius -> 0 the pinhole's convention).  The two lens numbers are drawn from the pixel's stream right behind the
+ * jitter's (at subframe 0 too).  "lt" connects cache vertex i to a lens point of its own (seed tea4(i, subframe), two numbers) with
+ * the importance spcbpt_camera_splat_lens states.
+ * With radius > 0: spcbpt_launch and spcbpt_launch_deferred of "SPCBPT_eye" (timed kernel), "pt" and "lt" render through the lens.
+ * SPCBPT_ERR_STATE, with a message naming the lens, from the forms that have no lens kernel -- none renders a pinhole image silently:
+ * spcbpt_launch_eye_batch, spcbpt_launch_adaptive, "SPCBPT_no_rmis", the counting variants (spcbpt_enable_counters, classifier trees
+ * with direction nodes) and "SPCBPT_eye" under SPCBPT_ENV_EYE_SEES_SKY.  The light pass, the sampler build and pretrace / preprocess
+ * keep the pinhole at `eye` (they shape the sampling, not the estimate); spcbpt_launch_features, the denoisers and the history
+ * reprojection use the centre-of-lens ray: their depth and normal are those of the sharp image.  A radius that pushes lens points
+ * through geometry is the caller's business.  The lens survives spcbpt_set_camera* and spcbpt_resize.
+ * SPCBPT_ERR_INVALID_ARG for a non-finite value, a negative radius or a focus <= 0. */
+int spcbpt_set_lens(spcbpt_ctx* ctx, float radius, float focus);
+int spcbpt_get_lens(spcbpt_ctx* ctx, float* radius, float* focus);   /* either pointer may be NULL; (0, 0) before the first spcbpt_set_lens */
+/* The eye side on the host: n samples, pixel xy[2 i], xy[2 i + 1], jitter and lens numbers two floats each -> origin and direction,
+ * three floats each.  Float32, no context and no GPU needed: the function the kernels call.  radius 0: `eye` and the pinhole direction. */
+int spcbpt_camera_lens_ray_host(const float eye[3], const float U[3], const float V[3], const float W[3], int width, int height, int n,
+                                const int32_t* xy, const float* jitter, const float* lens, float radius, float focus,
+                                float* origin, float* dir);
+/* The light side on the host: n world points (three floats each), each seen through the lens point of its two lens numbers.  With
+ * c = point - O and g = c . (U x V) / D (g <= 0: rejected), q = (focus / g) c reaches the point F where the line O -> point meets the
+ * plane in focus; (dx, dy) and the pixel are those of F (outside the image: rejected), and
+ *   weight = width height |q|^3 / (4 focus^2 |q . (U x V)|)
+ * is the reciprocal solid angle, seen from O, of the pixel's footprint on that plane.  inside[i] = 1 and dxdy / pixel (two each) /
+ * weight filled, or 0 (zeros, pixel -1); dxdy, pixel and weight may be NULL.  radius 0: spcbpt_camera_splat, bit for bit. */
+int spcbpt_camera_splat_lens(const float eye[3], const float U[3], const float V[3], const float W[3], int width, int height, int n,
+                             const float* points, const float* lens, float radius, float focus,
+                             float* dxdy, int32_t* pixel, float* weight, int32_t* inside);
+/* The numbers a kernel draws for the camera: out = (jx, jy, u1, u2).  with_jitter != 0: the stream of pixel index = y * width + x
+ * (jitter 0.5 and no draw for it at subframe 0); with_jitter == 0: the stream of cache slot `index` of "lt" (jx = jy = 0.5). */
+int spcbpt_lens_sample_host(uint32_t index, uint32_t subframe, int with_jitter, float out[4]);
+/* Debug: the device's own lens rays of `subframe`, eight floats per pixel of the film (origin xyz, direction xyz, 0, 0), from the
+ * device function the lens kernels call.  Synchronous; the film is not touched. */
+int spcbpt_debug_lens_rays(spcbpt_ctx* ctx, uint32_t subframe, float* out8);
+
 /* Replaces MyThrustOp::LVC_Process (cuda_thrust/device_thrust.cu:241-332):
  * builds cmfs / jump_buffer / Subspace[1000] / vertex_count / path_count from
  * the LVC currently held by the context, on the device. Asynchronous. */

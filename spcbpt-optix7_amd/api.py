@@ -377,6 +377,55 @@ def camera_splat(eye, U, V, W, width, height, point):
     return dx.value, dy.value, px.value, py.value, we.value
 
 
+def camera_lens_ray_host(eye, U, V, W, width, height, xy, jitter, lens, radius, focus):
+    """spcbpt_camera_lens_ray_host: the thin-lens camera's eye side for n samples -- pixels xy (n, 2) int, jitter (n, 2) and lens
+    numbers (n, 2) in [0, 1) -> (origin (n, 3), direction (n, 3)) float32.  Host code in float32 -- the function the lens kernels
+    call; no GPU needed.  radius 0 gives `eye` and the pinhole direction."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W)]
+    xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+    n = xy.shape[0]
+    jitter = np.ascontiguousarray(jitter, dtype=np.float32).reshape(n, 2)
+    lens = np.ascontiguousarray(lens, dtype=np.float32).reshape(n, 2)
+    origin, direction = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    rc = lib.spcbpt_camera_lens_ray_host(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), int(width), int(height), n, xy.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         _fp(jitter), _fp(lens), float(radius), float(focus), _fp(origin), _fp(direction))
+    if rc != 0:
+        raise ValueError(f"spcbpt_camera_lens_ray_host: bad argument (rc={rc})")
+    return origin, direction
+
+
+def camera_splat_lens(eye, U, V, W, width, height, points, lens, radius, focus):
+    """spcbpt_camera_splat_lens: the thin-lens camera's light side for n world points (n, 3), each seen through the lens point of its
+    lens numbers (n, 2).  Returns (inside (n,) bool, dxdy (n, 2), pixel (n, 2) int32, weight (n,)); rows with inside False hold zeros
+    and pixel -1.  Host code in float32 -- the function the "lt" kernels call; no GPU needed.  radius 0 is camera_splat."""
+    lib = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (eye, U, V, W)]
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = points.shape[0]
+    lens = np.ascontiguousarray(lens, dtype=np.float32).reshape(n, 2)
+    dxdy, pixel = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.int32)
+    weight, inside = np.zeros(n, np.float32), np.zeros(n, np.int32)
+    rc = lib.spcbpt_camera_splat_lens(_fp(a[0]), _fp(a[1]), _fp(a[2]), _fp(a[3]), int(width), int(height), n, _fp(points), _fp(lens), float(radius), float(focus),
+                                      _fp(dxdy), pixel.ctypes.data_as(C.POINTER(C.c_int32)), _fp(weight), inside.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise ValueError(f"spcbpt_camera_splat_lens: bad argument (rc={rc})")
+    return inside.astype(bool), dxdy, pixel, weight
+
+
+def lens_sample_host(index, subframe, with_jitter=True):
+    """spcbpt_lens_sample_host: (jx, jy, u1, u2) as a lens kernel draws them -- for pixel index y * width + x (with_jitter: the jitter
+    is 0.5 and draws nothing at subframe 0) or for cache slot `index` of "lt" (with_jitter=False).  `index` may be an array: (n, 4)."""
+    lib = load_library()
+    idx = np.atleast_1d(np.asarray(index, dtype=np.uint32))
+    out = np.zeros((idx.size, 4), np.float32)
+    row = (C.c_float * 4)()
+    for i, v in enumerate(idx.ravel()):
+        lib.spcbpt_lens_sample_host(int(v), int(subframe), 1 if with_jitter else 0, row)
+        out[i] = row[:]
+    return out if np.ndim(index) else out[0]
+
+
 def denoise_host(accum, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_c=0.0, sigma_n=0.0, sigma_x=0.0):
     """spcbpt_denoise_host: the a-trous denoiser of Renderer.denoise on (h, w, 4) float32 arrays as read_accum / read_features give
     them, seen through the camera (eye, U, V, W).  Host code in float32 -- the per-pixel function the kernels run; no GPU needed.
@@ -1004,6 +1053,12 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_trace_closest": [vp, vp, i32, vp, vp, vp],
         "spcbpt_trace_any": [vp, vp, i32, vp],
         "spcbpt_camera_splat": [f32p, f32p, f32p, f32p, i32, i32, f32p, f32p, f32p, C.POINTER(i32), C.POINTER(i32), f32p],
+        "spcbpt_set_lens": [vp, C.c_float, C.c_float],
+        "spcbpt_get_lens": [vp, f32p, f32p],
+        "spcbpt_camera_lens_ray_host": [f32p, f32p, f32p, f32p, i32, i32, i32, C.POINTER(C.c_int32), f32p, f32p, C.c_float, C.c_float, f32p, f32p],
+        "spcbpt_camera_splat_lens": [f32p, f32p, f32p, f32p, i32, i32, i32, f32p, f32p, C.c_float, C.c_float, f32p, C.POINTER(C.c_int32), f32p, C.POINTER(C.c_int32)],
+        "spcbpt_lens_sample_host": [C.c_uint32, C.c_uint32, i32, f32p],
+        "spcbpt_debug_lens_rays": [vp, C.c_uint32, f32p],
         "spcbpt_set_splat_order": [vp, i32],
         "spcbpt_get_splat_order": [vp, C.POINTER(i32)],
         "spcbpt_read_splat_records": [vp, f32p, C.POINTER(C.c_int32), i32, C.POINTER(i32)],
@@ -1127,6 +1182,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_build_source_hash", "spcbpt_build_arithmetic", "spcbpt_abi_struct_sizes", "spcbpt_lvc_export_on", "spcbpt_lvc_import_gathered", "spcbpt_lvc_export_batch_on", "spcbpt_lvc_import_gathered_batch", "spcbpt_film_pack_bands", "spcbpt_film_unpack_bands", "spcbpt_image_size", "spcbpt_get_light_trace", "spcbpt_enable_counters", "spcbpt_stream", "spcbpt_sync", "spcbpt_sync_light", "spcbpt_launch_deferred", "spcbpt_merge_deferred", "spcbpt_sync_film", "spcbpt_set_light_ahead", "spcbpt_get_pipeline_state", "spcbpt_reuse_sampler", "spcbpt_read_film", "spcbpt_debug_batch_scratch", "spcbpt_debug_read_sampling_tables", "spcbpt_lvc_import_wait", "spcbpt_kernel_time",
     "spcbpt_reset_kernel_time", "spcbpt_enable_kernel_timing", "spcbpt_trace_closest", "spcbpt_trace_any", "spcbpt_camera_splat",
     "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
+    "spcbpt_set_lens", "spcbpt_get_lens", "spcbpt_camera_lens_ray_host", "spcbpt_camera_splat_lens", "spcbpt_lens_sample_host", "spcbpt_debug_lens_rays",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
@@ -1202,6 +1258,25 @@ class Renderer:
     def resize(self, w, h):
         self._chk(self.lib.spcbpt_resize(self.h, w, h), "resize")
         self.width, self.height = w, h
+
+    def set_lens(self, radius, focus=1.0):
+        """spcbpt_set_lens: a thin lens of `radius` (world units) focused at depth `focus` (units of W; 1 = the plane through lookat).
+        radius 0, the default, is the pinhole.  "SPCBPT_eye" (timed kernel), "pt" and "lt" render through it; the batched, adaptive,
+        counting, sky-seeing and no_rmis forms refuse while it is set.  Survives set_camera* and resize."""
+        self._chk(self.lib.spcbpt_set_lens(self.h, float(radius), float(focus)), "set_lens")
+
+    def lens(self):
+        """(radius, focus) as set; (0.0, 0.0) before the first set_lens."""
+        r, f = C.c_float(), C.c_float()
+        self._chk(self.lib.spcbpt_get_lens(self.h, C.byref(r), C.byref(f)), "get_lens")
+        return r.value, f.value
+
+    def lens_rays(self, subframe=0):
+        """spcbpt_debug_lens_rays: (origin (h, w, 3), direction (h, w, 3)) of every pixel's lens ray of `subframe`, from the device
+        function the lens kernels call."""
+        out = np.zeros((self.height, self.width, 8), np.float32)
+        self._chk(self.lib.spcbpt_debug_lens_rays(self.h, int(subframe), _fp(out)), "debug_lens_rays")
+        return out[..., 0:3].copy(), out[..., 3:6].copy()
 
     def set_subspace(self, eye_tree=None, light_tree=None, q=None, cmf_gamma=None):
         if eye_tree is None and light_tree is None and q is None and cmf_gamma is None:

@@ -339,6 +339,7 @@ int spcbpt_set_camera(spcbpt_ctx* c, const float eye[3], const float U[3], const
     if (!eye || !U || !V || !W) { c->error = "null camera vector"; return SPCBPT_ERR_INVALID_ARG; }
     memcpy(c->kp.eye, eye, 12); memcpy(c->kp.U, U, 12); memcpy(c->kp.V, V, 12); memcpy(c->kp.W, W, 12);
     c->have_camera = true;
+    c->update_lens_axes();   // (ctx_lens.hip: the lens stays, its axes follow the frame)
     return SPCBPT_OK;
 }
 
@@ -414,7 +415,7 @@ int spcbpt_set_environment_mode(spcbpt_ctx* c, int flags) {
     if (c->deferred.active) { c->error = "set_environment_mode: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (c->sync_all()) return SPCBPT_ERR_HIP;
     c->kp.scene.env.mode = flags;
-    c->blocks_per_cu[0] = c->blocks_per_cu_batch = 0;   // the timed eye launches may change instantiation: ask again
+    c->blocks_per_cu[0] = c->blocks_per_cu_batch = c->blocks_per_cu_lens = 0;   // the timed eye launches may change instantiation: ask again
     return SPCBPT_OK;
 }
 int spcbpt_get_environment_mode(spcbpt_ctx* c, int* flags) {

@@ -10,6 +10,7 @@
 //   ctx_bloom.hip     Context + extern "C": the bloom stage -- a multi-scale glare ahead of the display transform
 //   ctx_local_tone.hip Context + extern "C": the local tone stage -- base / detail through a bilateral grid, ahead of the display transform
 //   ctx_history.hip   Context + extern "C": history capture, reprojection into the current view, resolve
+//   ctx_lens.hip      Context + extern "C": the thin-lens camera -- its parameters, the host forms of camera_lens.h, the debug ray kernel
 //   ctx_adaptive.hip  Context + extern "C": adaptive sampling -- tile counts, tile selection, the list-fed eye launch and its merge
 //   capi.hip          extern "C": create / destroy, state, launches by name
 //   capi_exchange.hip extern "C": LVC export / import, film band packing

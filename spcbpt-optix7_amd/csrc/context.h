@@ -257,6 +257,7 @@ struct Context {
     DevBuf<uint32_t> d_work_counter;   // tile queues of the render streams, then the core queues of the two light lanes
     int num_cus = 0, blocks_per_cu[3] = {0, 0, 0};   // per kernel variant (single-frame launches), of the instantiation launched
     int blocks_per_cu_batch = 0;                       // the batched timed kernel's
+    int blocks_per_cu_lens = 0;                        // the thin-lens form's (k_spcbpt_lens<ENV>, by scene.general as launched)
     int grid_percent = 0;              // persistent grid as a share of the resident block slots; 0 = 94 with several render streams, else 100 (launch_render)
     int light_blocks_wide = -1;        // ... of a pass that has the GPU to itself (no passes ahead): a lane per core, at most four blocks per CU (SPCBPT_LIGHT_BLOCKS_WIDE)
     int light_blocks = -1;             // persistent grid of the light pass (SPCBPT_LIGHT_BLOCKS; default: one block per CU)
@@ -315,6 +316,11 @@ struct Context {
     // atomics) per render stream, allocated at the first "lt" launch of that stream after a resize.
     DevBuf<float> d_splat[kMaxRender];
     int launch_splat(uint32_t frame, int r0, int r1, int rs);
+    // Thin-lens camera (ctx_lens.hip; spcbpt_set_lens): the two numbers live in kp (lens_radius, lens_focus), which spcbpt_set_camera* and
+    // spcbpt_resize leave alone.  radius 0, the default, is the pinhole: every launcher then picks the kernels it always picked.
+    int set_lens(float radius, float focus);
+    void update_lens_axes();
+    int debug_lens_rays(uint32_t subframe, float* out8);
     // The ordered mode of "lt" (spcbpt_set_splat_order, off by default): every vertex's contribution stored in the vertex's own slot,
     // a stable radix sort of (pixel, slot) and a per-pixel sum in slot order -- no atomics, the same film bits on every run.  Per render
     // stream and cache slot 32 B (a float4 record, the sort's key and value double buffers) plus hipcub's temporary storage and 4 B for

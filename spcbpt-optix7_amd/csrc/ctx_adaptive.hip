@@ -90,6 +90,7 @@ int Context::adaptive_set_tiles(const uint32_t* tiles, int n) {
 // ordinary launch -- it waits for the chain's last link itself.  The kernel-time spans are "adaptive_eye" and "adaptive_merge".
 int Context::launch_adaptive(const char* alg) {
     if (!alg || std::string(alg) != "SPCBPT_eye") { error = "launch_adaptive: \"SPCBPT_eye\" only (adaptive forms of \"pt\" and \"lt\" do not exist)"; return SPCBPT_ERR_INVALID_ARG; }
+    if (kp.lens_radius > 0.0f) { error = "launch_adaptive: the list-fed eye kernel has no lens form (spcbpt_set_lens): set the lens radius to 0"; return SPCBPT_ERR_STATE; }
     if (!adaptive.active) { error = "launch_adaptive: adaptive sampling is not active (spcbpt_adaptive_begin)"; return SPCBPT_ERR_STATE; }
     if (int rc = film_ready()) return rc;
     if (!have_sampler || !have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }

@@ -54,6 +54,19 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
                 "eye-sees-sky strategy: clear SPCBPT_ENV_EYE_SEES_SKY (spcbpt_set_environment_mode) for this launch";
         return SPCBPT_ERR_STATE;
     }
+    // The thin-lens camera (spcbpt_set_lens) exists as the timed single-frame eye form and as the plain "pt" form: every other form
+    // refuses rather than render a pinhole image while a lens is set.
+    const bool lens = kp.lens_radius > 0.0f;
+    if (lens && full_mis) { error = "SPCBPT_no_rmis: not with a lens set (spcbpt_set_lens): its full-path weights assume the pinhole camera -- set the lens radius to 0 for this launch"; return SPCBPT_ERR_STATE; }
+    if (lens && (spcbpt_alg ? kernel_variant() != 0 : counting)) {
+        error = std::string(name) + ": the event-counting kernels (counters enabled, or classifier trees with direction nodes) have no lens form (spcbpt_set_lens): "
+                "disable the counters or set the lens radius to 0 for this launch";
+        return SPCBPT_ERR_STATE;
+    }
+    if (lens && spcbpt_alg && eye_sees_sky(kp)) {
+        error = "SPCBPT_eye: the eye-sees-sky kernels have no lens form (spcbpt_set_lens): clear SPCBPT_ENV_EYE_SEES_SKY (spcbpt_set_environment_mode) or set the lens radius to 0 for this launch";
+        return SPCBPT_ERR_STATE;
+    }
     int rc = begin_render(r0, r1, rs);
     if (rc) return rc;
     kp.subframe = frame;
@@ -80,6 +93,10 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
         kp.work_counter = d_work_counter + rk;
         HIP_TRY(this, hipMemsetAsync(d_work_counter + rk, 0, sizeof(uint32_t), rstream));
         const int generic = kernel_variant();
+        if (lens && !blocks_per_cu_lens) {
+            blocks_per_cu_lens = spcbpt_lens_blocks_per_cu(kp.scene.general != 0);
+            if (const char* e = getenv("SPCBPT_BLOCKS_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < blocks_per_cu_lens) blocks_per_cu_lens = v; }
+        }
         if (!blocks_per_cu[generic]) {
             blocks_per_cu[generic] = spcbpt_blocks_per_cu(generic, false, kp.scene.general != 0, eye_sees_sky(kp));
             // developer knob (occupancy experiments): fewer resident blocks per CU than the kernel's resources allow
@@ -100,12 +117,14 @@ int Context::launch_render(const char* name, bool spcbpt_alg, uint32_t frame, in
         // not work: by the time the host has the vertex count it waited for, that kernel has drained.
         // SPCBPT_GRID_PERCENT fixes the share; SPCBPT_TILES_PER_WAVE bounds the waves by the tile count (experiments).
         const int generic = kernel_variant();
-        int max_blocks = num_cus * blocks_per_cu[generic];
+        int max_blocks = num_cus * (lens ? blocks_per_cu_lens : blocks_per_cu[generic]);
         if (tiles_per_wave > 1) max_blocks = std::max(1, std::min(max_blocks, (int)(kp.n_tiles / (uint32_t)(4 * tiles_per_wave))));
         const int percent = grid_percent > 0 ? grid_percent : (n_render > 1 ? 94 : 100);
         if (percent < 100) max_blocks = std::max(1, max_blocks * percent / 100);
-        launch_spcbpt(kp, generic, max_blocks, rstream);
+        if (lens) launch_spcbpt_lens(kp, max_blocks, rstream);   // (its grid is at most the tile range's: the spill area above covers it)
+        else launch_spcbpt(kp, generic, max_blocks, rstream);
     }
+    else if (lens) launch_pt_lens(kp, rstream);
     else launch_pt(kp, counting, rstream);
     time_end();
     HIP_TRY(this, hipGetLastError());
@@ -151,6 +170,7 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
                 "pass and fills no buckets (use spcbpt_launch per frame)";
         return SPCBPT_ERR_STATE;
     }
+    if (kp.lens_radius > 0.0f) { error = "launch_eye_batch: the batched eye kernel has no lens form (spcbpt_set_lens): use spcbpt_launch per frame, or set the lens radius to 0"; return SPCBPT_ERR_STATE; }
     if (!have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
     if (n < 1 || n > kMaxBatchFrames || !subframes) { error = "launch_eye_batch: 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
     if (n > (int)built_sets.size()) { error = "launch_eye_batch: fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }

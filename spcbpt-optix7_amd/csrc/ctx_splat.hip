@@ -48,6 +48,7 @@ int Context::launch_splat(uint32_t frame, int r0, int r1, int rs) {
     sp.lvc = sets[eset].lvc; sp.sampler_counts = sets[eset].counts; sp.capacity = capacity;
     sp.splat = d_splat[rk]; sp.result = kp.result;
     sp.spill = kp.spill; sp.spill_entries = kp.spill_entries; sp.diag = kp.diag;
+    sp.lens_radius = kp.lens_radius; sp.lens_focus = kp.lens_focus; memcpy(sp.lens_u, kp.lens_u, 12); memcpy(sp.lens_v, kp.lens_v, 12);   // spcbpt_set_lens: radius > 0 selects the lens kernels (kernels_splat.hip)
     if (!ordered) {
         HIP_TRY(this, hipMemsetAsync(d_splat[rk], 0, px * 16, rstream));
         time_begin("lt", rstream);

@@ -246,7 +246,7 @@ int Context::set_environment(const float* rgba, int w, int h, const float* cente
     V.project_pdf = (float)(1 / (3.14159265358979323846 * V.r * V.r));
     V.valid = 1;
     kp.scene.general = 1;
-    blocks_per_cu[0] = blocks_per_cu_batch = 0;   // other instantiations from now on: ask again
+    blocks_per_cu[0] = blocks_per_cu_batch = blocks_per_cu_lens = 0;   // other instantiations from now on: ask again
     kp.scene.lights = d_lights; kp.scene.n_lights = n_lights;
     // every cache traced so far is without sky vertices
     have_sampler = false; pending.clear(); built_sets.clear(); lvc_count = 0;

@@ -3,6 +3,7 @@
 // include this header, and the kernels here take a parameter block of their own (SplatParams), so KParams and the timed kernels'
 // code stay as they are.
 #pragma once
+#include "camera_lens.h"
 #include "camera_splat.h"
 #include "device_lib.h"
 
@@ -29,6 +30,9 @@ struct SplatParams {  // passed by value as the kernel argument block of the ker
     const uint32_t* keys_sorted;
     const uint32_t* vals_sorted;
     int32_t bound;                         // host-known upper bound of min(sampler_counts[0], capacity), <= capacity
+    // thin-lens camera (spcbpt_set_lens; appended): the LENS forms of the kernels only -- the host launches them when lens_radius > 0
+    float lens_radius, lens_focus;
+    float lens_u[3], lens_v[3];            // the lens axes (camera_lens_axes), as in KParams
 };
 
 // is row y one of the launch's rows? (lane_pixel / tile_pixel of eye_walk.h enumerate exactly these)
@@ -50,16 +54,31 @@ struct SplatJob {
 // not finite); true = `job` holds its shadow ray and what to add when the ray is clear:
 //   contrib = (flux / pdf) fb |n . toCam| / |c|^2  We / path_count,  fb = the light-side factor of connect_vertices (dev_rmis.h)
 // No clamp (the eye kernels' ISINVALIDVALUE cut at 100 000 would bias a pure estimator); non-finite values are dropped.
-SPC_DEV bool splat_cull(const SplatParams& p, const LightVertex& b, float path_count, SplatJob& job) {
+// LENS (camera_lens.h): the vertex of cache slot `slot` draws a lens point O of its own -- seed tea4(slot, subframe), two numbers, so the
+// draw is a function of the slot and the subframe alone, whatever thread looks at it -- and O stands where the eye stands in the pinhole
+// form: the projection goes through O onto the plane in focus, and toCam, |c|^2, the cosine and the shadow ray end at O.  One lens sample
+// per vertex is unbiased: the lens density 1 / area cancels against the 1 / area of the film's mean over the lens.
+template <bool LENS>
+SPC_DEV bool splat_cull(const SplatParams& p, const LightVertex& b, uint32_t slot, float path_count, SplatJob& job) {
     if (b.pad & SPCBPT_LV_DIRECTION) return false;   // a sky direction has no position (the host refuses "lt" with an environment map)
     const f3 bflux = ld3(b.flux);
     if (bflux.x == 0.0f && bflux.y == 0.0f && bflux.z == 0.0f) return false;
     float dx, dy, we;
     int px, py;
-    if (!camera_splat(p.eye, p.U, p.V, p.W, (int)p.width, (int)p.height, b.position, dx, dy, px, py, we)) return false;
+    f3 cam = ld3(p.eye);
+    if (LENS) {
+        uint32_t seed = tea4(slot, p.subframe);
+        const float u1 = rnd(seed);
+        const float u2 = rnd(seed);
+        float off[3];
+        camera_lens_point(p.lens_u, p.lens_v, u1, u2, off);
+        if (!camera_splat_lens_at(p.eye, p.U, p.V, p.W, (int)p.width, (int)p.height, b.position, off, p.lens_focus, dx, dy, px, py, we)) return false;
+        cam = mk3(p.eye[0] + off[0], p.eye[1] + off[1], p.eye[2] + off[2]);   // (O as camera_splat_lens_at forms it)
+    }
+    else if (!camera_splat(p.eye, p.U, p.V, p.W, (int)p.width, (int)p.height, b.position, dx, dy, px, py, we)) return false;
     if (!splat_row_selected(p, py)) return false;
     const f3 bpos = ld3(b.position), bn = ld3(b.normal);
-    const f3 bias = ld3(p.eye) - bpos;            // the shadow ray of k_pt: visA = vertex, visB = eye
+    const f3 bias = cam - bpos;                   // the shadow ray of k_pt: visA = vertex, visB = eye (LENS: the lens point)
     const float r2 = dot(bias, bias);
     const float len = sqrtf(r2);
     const f3 toCam = bias / len;

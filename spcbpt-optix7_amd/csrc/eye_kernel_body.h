@@ -1,5 +1,5 @@
 // The body of the eye megakernel (kernels.hip: k_spcbpt, k_spcbpt_sky), included INSIDE each __global__ function -- no #pragma once.
-// It reads the kernel's parameter `p` and the compile-time flags COUNT, BATCH, CACHE, ENV, SKY and TILES of the including kernel.  (As the
+// It reads the kernel's parameter `p` and the compile-time flags COUNT, BATCH, CACHE, ENV, SKY, TILES and LENS of the including kernel.  (As the
 // body of one force-inlined device function called by both kernels the timed forms came out with other code: the kernel argument
 // is then reached through a generic pointer, and the early passes schedule around it differently.  Included, k_spcbpt<...> is
 // compiled from the same statements as before SKY existed: tests/test_codegen_guard.py, tools/codegen_diff_symbols.py.)
@@ -111,8 +111,11 @@
                     alive = true;
                     has_ray = true;
                     fresh = true;
-                    w.dir = camera_ray(p, nx, ny, w.seed, TILES ? pool_sample : (BATCH ? p.frames[fid].subframe : p.subframe));
-                    w.origin = ld3(p.eye);
+                    if (LENS) w.dir = camera_ray_lens(p, nx, ny, w.seed, p.subframe, w.origin);   // (dev_lens.h: the lens point, and the ray through the sample's focus point)
+                    else {
+                        w.dir = camera_ray(p, nx, ny, w.seed, TILES ? pool_sample : (BATCH ? p.frames[fid].subframe : p.subframe));
+                        w.origin = ld3(p.eye);
+                    }
                     w.done = false;
                     w.next_flux = mk3(0.0f);
                     w.next_single_pdf = 1.0f;
@@ -144,13 +147,14 @@
         const uint32_t ids_b = (uint32_t)cur.c.mat | ((uint32_t)cur.lsub << 16);
         HitRec h;
         // (the next segment starts at the path's last vertex -- or at the camera for a path that was started in this iteration, whose
-        // `cur` still holds the parked path's vertex: w.origin would be a copy kept alive across the pass for nothing)
+        // `cur` still holds the parked path's vertex: w.origin would be a copy kept alive across the pass for nothing.  LENS: the camera is
+        // the lane's own lens point, which only w.origin holds -- that form keeps the three registers from the regeneration to init_EyeSubpath)
         // Issue priority by phase (s_setprio): the traversal pass is the phase whose instructions are the kernel's throughput (three quarters
         // of what it issues), connect and shading are chains of dependent fetches with little to issue in between -- a wave in the pass
         // goes first when both are ready.  Measured (profiles/r05_experiments.md, section 16): pass 1 / others 0: +1.1 % paths per second;
         // any phase but the pass raised: the light pass that shares the CUs (priority 0 throughout) starves and the step gets longer.
         if (SPC_PRIO_TRAV != SPC_PRIO_SHADE) __builtin_amdgcn_s_setprio(SPC_PRIO_TRAV);
-        trace_pool(S, st, alive && has_ray, fresh ? ld3(p.eye) : cur.c.pos, w.dir, h, w_org, w_ray, w_next, w_job, n_rays, cn, s_hot, EYE_HOT);
+        trace_pool(S, st, alive && has_ray, fresh ? (LENS ? w.origin : ld3(p.eye)) : cur.c.pos, w.dir, h, w_org, w_ray, w_next, w_job, n_rays, cn, s_hot, EYE_HOT);
         if (SPC_PRIO_CONNECT != SPC_PRIO_TRAV) __builtin_amdgcn_s_setprio(SPC_PRIO_CONNECT);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -258,7 +262,7 @@
         }
         if (fresh) {  // init_EyeSubpath (raygen.cu:216-231)
             fresh = false;
-            cur.c.pos = ld3(p.eye); cur.c.n = w.dir; cur.c.color = mk3(0.0f); cur.c.lastPos = cur.c.pos; cur.c.lnp = 0.0f; cur.c.mat = 0; cur.c.lld = false;
+            cur.c.pos = LENS ? w.origin : ld3(p.eye); cur.c.n = w.dir; cur.c.color = mk3(0.0f); cur.c.lastPos = cur.c.pos; cur.c.lnp = 0.0f; cur.c.mat = 0; cur.c.lld = false;
             cur.flux = mk3(1.0f); cur.R3 = mk3(0.0f); cur.pdf = 1.0f; cur.singlePdf = 1.0f; cur.sub = 0; cur.lastZone = 0; cur.depth = 0; cur.lsub = 0;
         }
         has_vertex = false;

@@ -14,7 +14,12 @@ int spcbpt_blocks_per_cu(int variant, bool batch, bool general, bool sky);   // 
 bool eye_sees_sky(const KParams& p);
 int render_tile_count(const KParams& p);
 void launch_pt(const KParams& p, bool count, hipStream_t s);
+void launch_pt_lens(const KParams& p, hipStream_t s);   // p.lens_radius > 0: k_pt_lens (no counting form)
 void launch_film_merge(const KParams& p, hipStream_t s);
+// the thin-lens eye form (k_spcbpt_lens<ENV>; p.lens_radius > 0, timed variant, single frame): launcher, persistent-grid size and occupancy
+void launch_spcbpt_lens(const KParams& p, int max_blocks, hipStream_t s);
+int spcbpt_lens_blocks(const KParams& p, int max_blocks);
+int spcbpt_lens_blocks_per_cu(bool general);
 void launch_light_trace(const KParams& p, int variant, int max_blocks, hipStream_t s);
 struct CompactBatch { LightVertex* lvc[kMaxBatchFrames]; int* counts[kMaxBatchFrames]; };   // per frame of a batched light pass: compact LVC + (vertex_count, path_count) of its set
 void launch_lvc_compact_batch(const LightVertex* scratch, const int* core_counts, const int* core_offsets, const int* path_counts, int core_count,

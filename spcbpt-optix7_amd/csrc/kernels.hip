@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_lib.h"
+#include "dev_lens.h"
 #include "eye_walk.h"
 #include "job_order.h"
 #include "kernel_config.h"
@@ -69,14 +70,14 @@ static_assert(STACK_LDS >= 16, "the pooled connections publish 16 dwords per eye
 template <bool COUNT, bool BATCH, bool CACHE, bool ENV = true>
 __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt(const KParams p) {
     constexpr bool SKY = false;   // escaped eye paths end unseen (__miss__BDPTVertex), as upstream
-    constexpr bool TILES = false;
+    constexpr bool TILES = false, LENS = false;
 #include "eye_kernel_body.h"
 }
 // SKY: the escaped eye paths see the environment map (eye_sky_miss; spcbpt_set_environment_mode, SPCBPT_ENV_EYE_SEES_SKY) -- the timed
 // form of a scene with a sky (label caching, no counters), a kernel of its own so that the k_spcbpt forms keep their code
 template <bool BATCH>
 __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_sky(const KParams p) {
-    constexpr bool COUNT = false, CACHE = true, ENV = true, SKY = true, TILES = false;
+    constexpr bool COUNT = false, CACHE = true, ENV = true, SKY = true, TILES = false, LENS = false;
 #include "eye_kernel_body.h"
 }
 // TILES: adaptive sampling (spcbpt_launch_adaptive).  The queue is p.tile_list[0 .. p.n_tiles) instead of a tile range, and the pixels of
@@ -85,119 +86,30 @@ __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_sky(const K
 // through film_write into p.result), a kernel of its own so that the k_spcbpt forms keep their code.
 template <bool ENV>
 __global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_tiles(const KParams p) {
-    constexpr bool COUNT = false, BATCH = false, CACHE = true, SKY = false, TILES = true;
+    constexpr bool COUNT = false, BATCH = false, CACHE = true, SKY = false, TILES = true, LENS = false;
+#include "eye_kernel_body.h"
+}
+// LENS: the thin-lens camera (spcbpt_set_lens with a radius > 0; camera_lens.h).  Every pixel-sample starts at a lens point of its own
+// (camera_ray_lens: two more random numbers behind the jitter's) and aims at the sample's point on the plane in focus; the rest of the
+// walk is the pinhole form's.  The timed single-frame form (label caching, no counters), a kernel of its own so that the k_spcbpt forms
+// keep their code: it alone carries the camera position in registers across the traversal pass (eye_kernel_body.h).
+template <bool ENV>
+__global__ __launch_bounds__(EYE_BLOCK, SPC_EYE_WAVES) void k_spcbpt_lens(const KParams p) {
+    constexpr bool COUNT = false, BATCH = false, CACHE = true, SKY = false, TILES = false, LENS = true;
 #include "eye_kernel_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
 template <bool COUNT>
 __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_pt(const KParams p) {
-    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
-    uint32_t x, y;
-    const bool active = lane_pixel(p, x, y);
-    Counts<COUNT> cn;
-    cn.clear();
-    if (active) {
-        const DeviceScene& S = p.scene;
-        TravStack<BLOCK, STACK_LDS> st;
-        st.init(s_stack, p.spill, p.spill_entries, (size_t)blockIdx.x * BLOCK + threadIdx.x, p.diag);
-        uint32_t seed;
-        f3 dir = camera_ray(p, x, y, seed);
-        f3 origin = ld3(p.eye);
-        f3 throughput = mk3(1.0f), result = mk3(0.0f);
-        float prd_pdf = 0.0f;
-        int depth = 0;
-        bool done = false;
-        cn.add(C_PIX); cn.add(C_EYE);
-        while (true) {
-            HitRec h;
-            cn.add(C_CLOSEST);
-            f3 current = mk3(0.0f), visA = mk3(0.0f), visB = mk3(0.0f);
-            if (!traverse<false, COUNT>(S, st, origin, dir, kEps, 1e16f, h, cn)) {
-                done = true;  // __miss__constant_radiance (raygen.cu:687-697): the sky is seen by primary rays only
-                if (depth == 0 && S.env.valid) result = throughput * env_color(S.env, dir);
-            } else {
-                const Geom g = local_geometry(S, h);
-                Pbr pbr = load_pbr(S, g.mat);
-                if (g.emitter) {  // __closesthit__lightsource
-                    const DLight& L = S.lights[pbr.light_id];
-                    const LightSampleD ls = area_light_at_hit(S, L, g);
-                    if (dot(dir, ls.normal) <= 0) {
-                        float mis = 1.0f;
-                        if (depth != 0) {
-                            const float pdf_hit = prd_pdf * fabsf(dot(dir, ls.normal)) / (h.t * h.t);
-                            mis = pdf_hit / (ls.pdf + pdf_hit);
-                        }
-                        result += throughput * ls.emission * mis;
-                    }
-                    done = true;
-                } else {  // __closesthit__radiance
-                    color_tex_sample(S, g, pbr, cn);
-                    f3 N = g.N;
-                    if (dot(N, dir) > 0.f) N = -N;
-                    const f3 in_dir = -dir;
-                    const float rr = clampf(max3(pbr.base), SPCBPT_MIN_RR_RATE, 1.0f);
-                    const int lid = pick_light(S, seed);
-                    const DLight& L = S.lights[lid];
-                    if (L.type == 1) {   // next-event estimation of the environment map (hit_program.cu:502-518)
-                        const f3 direction = env_sample(S.env, seed);
-                        const f3 emission = env_color(S.env, direction);
-                        const float lpdf = env_pdf(S.env, direction) / (float)S.n_lights;
-                        const f3 V = -normalize(dir);
-                        const float L_dot_N = dot(direction, N);
-                        if (L_dot_N > 0.0f) {
-                            // float3 + float adds the scalar to every component: as written upstream (q18); SPCBPT_ENV_PT_SKY_SHADOW_ALONG_DIR:
-                            // the point 2 r along the direction (the oracle's pt_env_nee_fixed)
-                            const bool along_dir = (S.env.mode & SPCBPT_ENV_PT_SKY_SHADOW_ALONG_DIR) != 0;
-                            visA = g.P; visB = along_dir ? g.P + direction * (S.env.r * 2) : g.P + direction + mk3(S.env.r * 2);
-                            const f3 eval = bsdf_eval(pbr, N, V, direction);
-                            current = throughput * emission / lpdf * eval * L_dot_N;
-                        }
-                    } else {
-                        const LightSampleD ls = area_light_sample(S, L, seed);
-                        const f3 dvec = ls.position - g.P;
-                        const float L_dist = sqrtf(dot(dvec, dvec));
-                        const f3 Ld = dvec / L_dist;
-                        const f3 V = -normalize(dir);
-                        const float L_dot_LN = dot(-Ld, ls.normal);
-                        const float N_dot_L = dot(N, Ld), N_dot_V = dot(N, V);
-                        if (N_dot_L > 0.0f && N_dot_V > 0.0f && L_dot_LN > 0.0f) {
-                            visA = g.P; visB = ls.position;
-                            const f3 eval = bsdf_eval(pbr, N, V, Ld);
-                            const float pdf_hit = bsdf_pdf(pbr, N, V, Ld) * fabsf(L_dot_LN) / (L_dist * L_dist) * rr;
-                            const float mis = ls.pdf / (pdf_hit + ls.pdf);
-                            current = throughput * ls.emission * 1.0f / ls.pdf * N_dot_L * L_dot_LN / L_dist / L_dist * eval * mis;
-                        }
-                    }
-                    origin = g.P;
-                    cn.add(C_VERTEX);
-                    if (rnd(seed) > rr) {
-                        done = true;
-                    } else {
-                        dir = bsdf_sample(pbr, N, in_dir, seed);
-                        const float pdf = bsdf_pdf(pbr, N, in_dir, dir);
-                        if (pdf > 0.0f) {
-                            throughput *= bsdf_eval(pbr, N, in_dir, dir) * fabsf(dot(dir, N)) / pdf / rr;
-                            prd_pdf = pdf * rr;
-                        } else {
-                            done = true;
-                        }
-                    }
-                }
-            }
-            if (sum3(current) > 0.0f) {  // the shadow ray is shot by raygen (raygen.cu:134-143)
-                const f3 bias = visB - visA;
-                const float len = sqrtf(dot(bias, bias));
-                HitRec sh;
-                cn.add(C_SHADOW);
-                if (!traverse<true, COUNT>(S, st, visA, bias / len, kEps, len - kEps, sh, cn)) result += current;
-            }
-            if (done || depth > 30) break;
-            depth += 1;
-        }
-        film_write(p, x, y, result);
-    }
-    cn.flush(p.counters);
+    constexpr bool LENS = false;
+#include "pt_kernel_body.h"
+}
+// ... with the thin-lens camera (spcbpt_set_lens): the primary ray starts at a lens point.  The plain form only, and a kernel of its own
+// name: the two k_pt<COUNT> instantiations keep their code and stay the only two (tests/test_codegen_mesh_light.py counts them).
+__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_pt_lens(const KParams p) {
+    constexpr bool COUNT = false, LENS = true;
+#include "pt_kernel_body.h"
 }
 
 // ---- host-callable launchers ---------------------------------------------------------------------
@@ -267,6 +179,26 @@ void launch_spcbpt_tiles(const KParams& p, int max_blocks, hipStream_t s) {
     if (blocks <= 0 || !p.tile_list || !p.tile_samples) return;
     if (p.scene.general) hipLaunchKernelGGL((k_spcbpt_tiles<true>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
     else hipLaunchKernelGGL((k_spcbpt_tiles<false>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+}
+// ... and of the thin-lens form (p.lens_radius > 0): the tile range of launch_spcbpt, timed variant only (the host refuses the others)
+int spcbpt_lens_blocks(const KParams& p, int max_blocks) {
+    const long long tiles = (long long)p.n_tiles;
+    if (tiles <= 0) return 0;
+    long long blocks = (tiles + (EYE_BLOCK / 64) - 1) / (EYE_BLOCK / 64);
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    return (int)blocks;
+}
+void launch_spcbpt_lens(const KParams& p, int max_blocks, hipStream_t s) {
+    const int blocks = spcbpt_lens_blocks(p, max_blocks);
+    if (blocks <= 0) return;
+    if (p.scene.general) hipLaunchKernelGGL((k_spcbpt_lens<true>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+    else hipLaunchKernelGGL((k_spcbpt_lens<false>), dim3((unsigned)blocks), dim3(EYE_BLOCK), 0, s, p);
+}
+int spcbpt_lens_blocks_per_cu(bool general) {
+    int n = 0;
+    const hipError_t e = general ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_spcbpt_lens<true>, EYE_BLOCK, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_spcbpt_lens<false>, EYE_BLOCK, 0);
+    return e == hipSuccess && n > 0 ? n : 1;
 }
 int spcbpt_tiles_blocks_per_cu(bool general) {
     int n = 0;
@@ -352,6 +284,11 @@ void launch_pt(const KParams& p, bool count, hipStream_t s) {
     if (blocks <= 0) return;
     if (count) hipLaunchKernelGGL(k_pt<true>, dim3(blocks), dim3(BLOCK), 0, s, p);
     else hipLaunchKernelGGL(k_pt<false>, dim3(blocks), dim3(BLOCK), 0, s, p);
+}
+void launch_pt_lens(const KParams& p, hipStream_t s) {
+    const int blocks = render_blocks(p);
+    if (blocks <= 0) return;
+    hipLaunchKernelGGL(k_pt_lens, dim3(blocks), dim3(BLOCK), 0, s, p);
 }
 
 }  // namespace spc

@@ -21,8 +21,10 @@ namespace spc {
 // whose vertex happened to survive.  A clear ray adds its contribution with three float atomics (12 B; a frame adds a few hundred
 // thousand of them -- far below the chip's float-atomic rate, so nothing is pre-reduced on chip).  The sums depend on the order of
 // arrival in the last bits: in this, the atomic mode, the film of "lt" is not bit-reproducible from run to run.
-__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_splat(const SplatParams p) {
-    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+// LENS (spcbpt_set_lens with a radius > 0): splat_cull<true> connects every vertex to a lens point of its own; a kernel of its own
+// (k_lt_splat_lens below), so that the pinhole launch runs the pinhole code.
+template <bool LENS>
+SPC_DEV void lt_splat_walk(const SplatParams& p, uint32_t* s_stack) {
     const DeviceScene& S = p.scene;
     const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     TravStack<BLOCK, STACK_LDS> st;
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_splat(const SplatParams
             float4 q[6];
 #pragma unroll
             for (int k = 0; k < 6; k++) q[k] = src[k];
-            live = splat_cull(p, *reinterpret_cast<const LightVertex*>(q), path_count, job);
+            live = splat_cull<LENS>(p, *reinterpret_cast<const LightVertex*>(q), (uint32_t)i, path_count, job);
             i += stride;
         }
         if (!__any(live)) break;   // every lane's share of the queue is dry and nobody holds a ray
@@ -54,6 +56,14 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_splat(const SplatParams
             }
         }
     }
+}
+__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_splat(const SplatParams p) {
+    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+    lt_splat_walk<false>(p, s_stack);
+}
+__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_splat_lens(const SplatParams p) {
+    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+    lt_splat_walk<true>(p, s_stack);
 }
 
 // The splat buffer as this subframe's radiance: film_write into `result`, from where the ordinary film merge (k_film_merge: running
@@ -79,8 +89,9 @@ SPC_DEV void splat_record_store(const SplatParams& p, uint32_t slot, f3 rgb, uin
     p.keys[slot] = key;
     p.vals[slot] = slot;
 }
-__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_records(const SplatParams p) {
-    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+// (LENS: a slot's lens point is a function of the slot and the subframe -- splat_cull -- so the records stay a function of the cache)
+template <bool LENS>
+SPC_DEV void lt_records_walk(const SplatParams& p, uint32_t* s_stack) {
     const DeviceScene& S = p.scene;
     const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     TravStack<BLOCK, STACK_LDS> st;
@@ -101,7 +112,7 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_records(const SplatPara
                 float4 q[6];
 #pragma unroll
                 for (int k = 0; k < 6; k++) q[k] = src[k];
-                live = splat_cull(p, *reinterpret_cast<const LightVertex*>(q), path_count, job);
+                live = splat_cull<LENS>(p, *reinterpret_cast<const LightVertex*>(q), (uint32_t)i, path_count, job);
             }
             if (live) job.index = (uint32_t)i;
             else splat_record_store(p, (uint32_t)i, mk3(0.0f), pad);
@@ -114,6 +125,14 @@ __global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_records(const SplatPara
             splat_record_store(p, job.index, clear ? job.contrib : mk3(0.0f), clear ? job.pixel : pad);
         }
     }
+}
+__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_records(const SplatParams p) {
+    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+    lt_records_walk<false>(p, s_stack);
+}
+__global__ __launch_bounds__(BLOCK, SPC_WAVES) void k_lt_records_lens(const SplatParams p) {
+    __shared__ uint32_t s_stack[BLOCK * STACK_LDS];
+    lt_records_walk<true>(p, s_stack);
 }
 
 // The ordered mode's last pass, in place of k_lt_resolve: one lane per pixel of the launch's rows finds its segment in the sorted
@@ -135,11 +154,13 @@ int splat_block_threads() { return BLOCK; }
 int splat_blocks(int max_blocks) { return max_blocks < 1 ? 1 : max_blocks; }
 void launch_lt_splat(const SplatParams& p, int blocks, hipStream_t s) {
     if (blocks <= 0 || p.capacity <= 0) return;
-    hipLaunchKernelGGL(k_lt_splat, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
+    if (p.lens_radius > 0.0f) hipLaunchKernelGGL(k_lt_splat_lens, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
+    else hipLaunchKernelGGL(k_lt_splat, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
 }
 void launch_lt_records(const SplatParams& p, int blocks, hipStream_t s) {
     if (blocks <= 0 || p.bound <= 0) return;
-    hipLaunchKernelGGL(k_lt_records, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
+    if (p.lens_radius > 0.0f) hipLaunchKernelGGL(k_lt_records_lens, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
+    else hipLaunchKernelGGL(k_lt_records, dim3((unsigned)blocks), dim3(BLOCK), 0, s, p);
 }
 // one wave per 8x8 tile of the selected bands, four tiles per block (render_blocks of kernels.hip)
 static int resolve_blocks(const SplatParams& p) {

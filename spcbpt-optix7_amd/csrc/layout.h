@@ -205,6 +205,10 @@ struct KParams {  // passed by value as the kernel argument block (the MyParams 
     // adaptive sampling (k_spcbpt_tiles only; appended, so that every other kernel finds its fields where they were)
     const uint32_t* tile_list;     // the queue: n_tiles tiles of the whole film (x-major, row_begin = 0, row_step = 1), strictly ascending
     const uint32_t* tile_samples;  // per tile of the film: the sample index its pixels draw next (what `subframe` is to an ordinary launch)
+    // thin-lens camera (k_spcbpt_lens, k_pt_lens and the debug ray kernel only; appended likewise): camera_lens.h
+    float lens_radius;             // world units; 0 = the pinhole (the launchers then keep the pinhole kernels)
+    float lens_focus;              // depth of the plane in focus, in units of W
+    float lens_u[3], lens_v[3];    // radius U / |U|, radius V / |V| (camera_lens_axes, computed by the host whenever the camera or the lens changes)
 };
 
 }  // namespace spc

@@ -12,6 +12,8 @@
 // --denoise-variance: the same with the variance-guided filter (spcbpt_denoise_variance; switches the film's moments on).
 // --target-error E [--check-every K]: switches the film's moments on and renders until spcbpt_film_error's mean is <= E (asked every K
 // frames, default 8, from the second frame on) or --frames is reached; prints the frames used and the error reached.
+// --aperture R [--focus F]: a thin-lens camera (spcbpt_set_lens) of radius R in world units, focused at depth F in units of the distance to
+// the camera's lookat point (default 1); "pt", "SPCBPT_eye" and "lt" render through it, --adaptive is refused by the library.
 // --adaptive (with --alg SPCBPT_eye and --target-error E) [--min-samples M] [--max-samples X] [--check-every K]: adaptive sampling.
 // max(M, 2) uniform frames, spcbpt_adaptive_begin, then rounds of spcbpt_adaptive_select followed by up to K (default 1) times (light
 // pass, sampler build, spcbpt_launch_adaptive) until the selection is empty or a tile would pass min(X, --frames) samples; prints the
@@ -29,7 +31,7 @@
 // --local-tone C [--local-detail D] [--local-cell S] [--local-range R]: that image -- after --bloom, if given -- goes through
 // spcbpt_local_tone (compress C in (0, 2], detail D, default 1, S = 4 .. 64 pixels per grid cell, default 16, R stops per bin, default 1)
 // and the local tone plane is what <out>_display.ppm shows; --local-tone alone implies the display pass with its defaults.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -70,7 +72,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -92,6 +94,7 @@ int main(int argc, char** argv) {
     bool local_tone = false;      // --local-tone C: the shown image goes through spcbpt_local_tone (after spcbpt_bloom, if both)
     spcbpt_local_tone_params ltp;
     spcbpt_local_tone_default_params(&ltp);
+    float aperture = 0.0f, focus = 1.0f;   // --aperture R [--focus F]: a thin lens of radius R (world units) focused at depth F (1 = the lookat plane)
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--alg" && i + 1 < argc) alg = argv[++i];
@@ -131,6 +134,8 @@ int main(int argc, char** argv) {
         else if (a == "--local-detail" && i + 1 < argc) ltp.detail = (float)atof(argv[++i]);
         else if (a == "--local-cell" && i + 1 < argc) ltp.cell = atoi(argv[++i]);
         else if (a == "--local-range" && i + 1 < argc) ltp.range = (float)atof(argv[++i]);
+        else if (a == "--aperture" && i + 1 < argc) aperture = (float)atof(argv[++i]);
+        else if (a == "--focus" && i + 1 < argc) focus = (float)atof(argv[++i]);
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -184,6 +189,10 @@ int main(int argc, char** argv) {
     CHECK(ctx, spcbpt_set_environment_mode(ctx, env_mode));
     CHECK(ctx, spcbpt_set_camera_lookat(ctx, eye, lookat, up, fov, (float)width / (float)height));
     CHECK(ctx, spcbpt_resize(ctx, width, height));
+    if (aperture != 0.0f) {   // (a bad value is the library's to refuse; so is --adaptive, which has no lens form)
+        CHECK(ctx, spcbpt_set_lens(ctx, aperture, focus));
+        printf("lens: radius %g, focus %g\n", aperture, focus);
+    }
     if (ordered_splat) {
         CHECK(ctx, spcbpt_set_splat_order(ctx, SPCBPT_SPLAT_ORDERED));
         printf("splat order: ordered (the film of \"lt\" is bit-reproducible)\n");
