@@ -560,7 +560,8 @@ int spcbpt_denoise_host(const float* accum_rgba, const float* albedo_rgba, const
  * in mid-film, n counts the merges since.  A dropped deferred frame updates nothing.  The variance of the mean of channel k is
  * M2_k / (n (n - 1)) for n >= 2.  The plane (16 B per pixel) is allocated and zeroed at the first merge after spcbpt_resize, freed
  * by spcbpt_resize and by switching off (which waits for the context's streams), zeroed by spcbpt_clear_accum.  While the switch is on
- * spcbpt_launch_eye_batch returns SPCBPT_ERR_STATE (its merge takes up to 32 frames per pixel in one pass and keeps no moments);
+ * spcbpt_launch_eye_batch returns SPCBPT_ERR_STATE (its merge takes up to 32 frames per pixel in one pass and keeps no moments;
+ * spcbpt_launch_eye_batch_film is the batched launch whose merge keeps them);
  * the N-GPU host (spcbpt_mgpu.h) and the viewer do not use the switch.  The kernel-time span of the updates is "moments". */
 int spcbpt_set_film_moments(spcbpt_ctx* ctx, int enabled);
 int spcbpt_get_film_moments(spcbpt_ctx* ctx, int* enabled);
@@ -601,7 +602,8 @@ int spcbpt_film_error_host(const float* accum_rgba, const float* m2n, int64_t n_
  * Independent of the moments switch; switched on in mid-film, the buckets count the merges since.  A dropped deferred frame updates
  * nothing.  The planes (16 K B per pixel) are allocated and zeroed at the first merge after spcbpt_resize, freed by spcbpt_resize
  * (K stays), by switching off and by changing K (both wait for the context's streams), zeroed by spcbpt_clear_accum.  While the
- * buckets are on, spcbpt_launch_eye_batch (its merge takes up to 32 frames per pixel in one pass) and spcbpt_adaptive_begin (its
+ * buckets are on, spcbpt_launch_eye_batch (its merge takes up to 32 frames per pixel in one pass and fills no buckets;
+ * spcbpt_launch_eye_batch_film is the batched launch whose merge fills them) and spcbpt_adaptive_begin (its
  * per-tile merge fills no buckets) return SPCBPT_ERR_STATE with a text that names the buckets; while adaptive sampling is active,
  * spcbpt_set_film_buckets returns SPCBPT_ERR_STATE.  Any other K: SPCBPT_ERR_INVALID_ARG.  The N-GPU host (spcbpt_mgpu.h), the
  * viewer and the checkpoints do not use the switch.  The kernel-time span of the updates is "buckets". */
@@ -1176,6 +1178,23 @@ int spcbpt_sync_film(spcbpt_ctx* ctx);
  * (SPCBPT_ERR_STATE otherwise).  SPCBPT_EYE_BATCH = F in the environment at spcbpt_create sizes the ring of sampler buffer
  * sets for batches of F, so that batches in flight, light passes ahead and builds never wait for a set. */
 int spcbpt_launch_eye_batch(spcbpt_ctx* ctx, int n_frames, const uint32_t* subframes, int row_begin, int row_end, int row_step);
+/* The same launch -- arguments, preconditions, eye kernel -- whose merge also keeps the film's second moment (spcbpt_set_film_moments)
+ * and fills its buckets (spcbpt_set_film_buckets), whichever are on: one pass in which every pixel takes the frames in order and does,
+ * per frame, exactly what the moments update, the bucket update and the merge of spcbpt_launch do.  accum, frame, the moment plane and
+ * the bucket planes are bit for bit those of n_frames spcbpt_launch("SPCBPT_eye") calls, so spcbpt_film_error, spcbpt_denoise_variance,
+ * spcbpt_adaptive_begin and spcbpt_robust_resolve see the film they would have seen.  With both switches off the call is
+ * spcbpt_launch_eye_batch.  SPCBPT_ERR_STATE with a text that names the reason while adaptive sampling is active, a deferred frame is
+ * outstanding, a lens is set, event counters are on or the classifier trees have direction nodes; SPCBPT_ERR_INVALID_ARG for n_frames
+ * outside 1 .. 32.  The kernel-time span of the merge is "film_merge_stats". */
+int spcbpt_launch_eye_batch_film(spcbpt_ctx* ctx, int n_frames, const uint32_t* subframes, int row_begin, int row_end, int row_step);
+/* That merge of n_pixels pixels on the host: the per-pixel function the kernel runs (float32, no contraction).  samples is
+ * [n][n_pixels] float4, the frames' samples in batch order with subframes[k] their subframe indices; accum_inout [n_pixels] float4 (its
+ * alpha becomes 1, as the film's); m2n_inout_or_null [n_pixels] float4, NULL = no moments; planes_inout_or_null [buckets][n_pixels]
+ * float4 with buckets = 3 .. 32, or buckets = 0 (the pointer is then ignored).  All updated in place.  No context and no GPU needed.
+ * SPCBPT_ERR_INVALID_ARG for a NULL samples / subframes / accum, n outside 1 .. 32, n_pixels outside 1 .. 2^28, buckets not 0 or
+ * 3 .. 32, or buckets without planes. */
+int spcbpt_film_merge_batch_host(const float* samples, const uint32_t* subframes, int n, int64_t n_pixels, int buckets,
+                                 float* accum_inout, float* m2n_inout_or_null, float* planes_inout_or_null);
 /* Batched light pass (no reference counterpart; needs spcbpt_set_light_ahead on): the "light trace" launches of launch frames
  * first_frame .. first_frame + n_frames - 1 as ONE persistent kernel whose core queue spans the frames.  Every pass lands in its own
  * buffer set and queues up exactly as n_frames spcbpt_launch("light trace", first_frame + k) calls would have left them -- the caches

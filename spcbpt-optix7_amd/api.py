@@ -609,6 +609,31 @@ def film_buckets_update_host(sample, subframe, planes):
     return planes
 
 
+def film_merge_batch_host(samples, subframes, accum, m2n=None, planes=None):
+    """spcbpt_film_merge_batch_host: the batched merge of launch_eye_batch_film on the host.  `samples` is (n, ..., 4) float32, the
+    frames' samples in batch order, `subframes` their n subframe indices; `accum` ((..., 4)), `m2n` ((..., 4), None = no moments) and
+    `planes` ((K, ..., 4), None = no buckets) are C-contiguous float32 arrays updated IN PLACE.  The per-pixel function the kernel
+    runs; no GPU needed."""
+    lib = load_library()
+    x = np.ascontiguousarray(samples, dtype=np.float32)
+    sf = np.ascontiguousarray(subframes, dtype=np.uint32).reshape(-1)
+    for name, a in (("accum", accum), ("m2n", m2n), ("planes", planes)):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]):
+            raise SpcbptError(f"film_merge_batch_host: {name} must be a C-contiguous float32 array (it is updated in place)")
+    if x.ndim < 2 or x.shape[-1] != 4 or x.shape[0] != len(sf) or accum.shape != x.shape[1:]:
+        raise SpcbptError("film_merge_batch_host: samples must be (n, ..., 4) with n = len(subframes) and accum (..., 4)")
+    if m2n is not None and m2n.shape != accum.shape:
+        raise SpcbptError("film_merge_batch_host: m2n must have accum's shape")
+    if planes is not None and (planes.ndim < 2 or planes.shape[1:] != accum.shape):
+        raise SpcbptError("film_merge_batch_host: planes must be (K, ..., 4) over accum's shape")
+    rc = lib.spcbpt_film_merge_batch_host(_fp(x), sf.ctypes.data_as(C.POINTER(C.c_uint32)), len(sf), accum.size // 4,
+                                          planes.shape[0] if planes is not None else 0, _fp(accum),
+                                          _fp(m2n) if m2n is not None else None, _fp(planes) if planes is not None else None)
+    if rc != 0:
+        raise SpcbptError(f"film_merge_batch_host failed ({rc})")
+    return accum
+
+
 def robust_resolve_host(planes, strength=1.0):
     """spcbpt_robust_resolve_host: the median-of-means resolve of bucket planes ((K, ..., 4) float32 as read_film_buckets gives them) at
     `strength` in [0, 8].  Returns (..., 4) float32: (r, g, b, w) with w the number of buckets kept.  The per-pixel function the
@@ -1081,6 +1106,8 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_get_film_buckets": [vp, C.POINTER(i32)],
         "spcbpt_read_film_buckets": [vp, vp],
         "spcbpt_film_buckets_update_host": [f32p, u32, i32, C.c_int64, f32p],
+        "spcbpt_film_merge_batch_host": [f32p, C.POINTER(u32), i32, C.c_int64, i32, f32p, f32p, f32p],
+        "spcbpt_launch_eye_batch_film": [vp, i32, C.POINTER(u32), i32, i32, i32],
         "spcbpt_robust_resolve": [vp, C.c_float],
         "spcbpt_read_robust": [vp, vp, vp],
         "spcbpt_robust_resolve_host": [f32p, i32, C.c_int64, C.c_float, f32p],
@@ -1175,7 +1202,7 @@ def load_library(path: str = LIB_PATH):
 
 EXPORTED_SYMBOLS = [
     "spcbpt_create", "spcbpt_create_lit", "spcbpt_mesh_light_struct_size", "spcbpt_light_info", "spcbpt_mesh_light_table", "spcbpt_scene_file_mesh_lights", "spcbpt_destroy", "spcbpt_last_error", "spcbpt_set_camera", "spcbpt_set_camera_lookat",
-    "spcbpt_resize", "spcbpt_set_subspace", "spcbpt_set_light_trace", "spcbpt_launch", "spcbpt_launch_eye_batch", "spcbpt_launch_light_batch", "spcbpt_build_sampler", "spcbpt_build_sampler_batch",
+    "spcbpt_resize", "spcbpt_set_subspace", "spcbpt_set_light_trace", "spcbpt_launch", "spcbpt_launch_eye_batch", "spcbpt_launch_eye_batch_film", "spcbpt_film_merge_batch_host", "spcbpt_launch_light_batch", "spcbpt_build_sampler", "spcbpt_build_sampler_batch",
     "spcbpt_lvc_export", "spcbpt_lvc_import", "spcbpt_lvc_set_capacity", "spcbpt_lvc_get_capacity", "spcbpt_set_environment", "spcbpt_get_environment", "spcbpt_set_environment_mode", "spcbpt_get_environment_mode", "spcbpt_hdr_load", "spcbpt_lvc_read", "spcbpt_sampler_read", "spcbpt_read_accum",
     "spcbpt_read_frame", "spcbpt_accum_device_ptr", "spcbpt_clear_accum", "spcbpt_get_counters",
     "spcbpt_reset_counters", "spcbpt_debug_phase_clocks", "spcbpt_debug_spill_arm", "spcbpt_debug_spill_count", "spcbpt_set_connection_sampler", "spcbpt_debug_unit", "spcbpt_debug_trace_bench", "spcbpt_debug_trace_pool",
@@ -1555,6 +1582,13 @@ class Renderer:
         sf = (C.c_uint32 * len(subframes))(*[int(v) for v in subframes])
         r0, r1, rs = rows if rows is not None else (0, self.height, 1)
         self._chk(self.lib.spcbpt_launch_eye_batch(self.h, len(subframes), sf, r0, r1, rs), "launch_eye_batch")
+
+    def launch_eye_batch_film(self, subframes, rows=None):
+        """launch_eye_batch whose merge keeps the film's second moment and fills its buckets, whichever are on
+        (spcbpt_launch_eye_batch_film): the film, the moments and the buckets of len(subframes) per-frame launches."""
+        sf = (C.c_uint32 * len(subframes))(*[int(v) for v in subframes])
+        r0, r1, rs = rows if rows is not None else (0, self.height, 1)
+        self._chk(self.lib.spcbpt_launch_eye_batch_film(self.h, len(subframes), sf, r0, r1, rs), "launch_eye_batch_film")
 
     def build_sampler(self):
         self._chk(self.lib.spcbpt_build_sampler(self.h), "build_sampler")

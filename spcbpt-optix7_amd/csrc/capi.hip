@@ -479,6 +479,10 @@ int spcbpt_launch_eye_batch(spcbpt_ctx* c, int n_frames, const uint32_t* subfram
     CTX_CHECK(c);
     return c->launch_eye_batch(n_frames, subframes, r0, r1, rs);
 }
+int spcbpt_launch_eye_batch_film(spcbpt_ctx* c, int n_frames, const uint32_t* subframes, int r0, int r1, int rs) {
+    CTX_CHECK(c);
+    return c->launch_eye_batch_film(n_frames, subframes, r0, r1, rs);
+}
 
 int spcbpt_build_sampler_batch(spcbpt_ctx* c, int n_builds) {
     CTX_CHECK(c);

@@ -312,6 +312,10 @@ struct Context {
     hipEvent_t ev_desc[kMaxRender][kDescRing] = {};              // upload out of that pinned slot done
     int desc_gen[kMaxRender] = {};
     int launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs);
+    // ... and the same launch whose merge keeps the film's second moment and fills its buckets (spcbpt_launch_eye_batch_film;
+    // kernels_merge_stats.hip).  batch_render is the body the two share: everything up to the merge, which `film` selects.
+    int launch_eye_batch_film(int n, const uint32_t* subframes, int r0, int r1, int rs);
+    int batch_render(const char* name, bool film, int n, const uint32_t* subframes, int r0, int r1, int rs);
     // "lt" (ctx_splat.hip): the cache of set `eset` splatted onto the film.  One splat buffer (float4 per pixel, summed with float
     // atomics) per render stream, allocated at the first "lt" launch of that stream after a resize.
     DevBuf<float> d_splat[kMaxRender];

@@ -1,10 +1,13 @@
 // Context: eye / pt launches (single, deferred, batched) and the film merges
 // (part of the C ABI library: see capi_common.h for the map of its translation units)
 #include "capi_common.h"
+#include "kernels_merge_stats.h"
 
 using namespace spc;
 
 namespace spc {
+
+static_assert(kMergeStatsMaxFrames == kMaxBatchFrames, "MergeStatsParams holds one slot per frame of a batch");
 
 // What every launch that ends in a film merge needs before anything else ...
 int Context::film_ready() {
@@ -156,29 +159,35 @@ int Context::sync_film() {
     return check_diag();
 }
 
-int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs) {
-    int rc = uniform_merge_allowed("launch_eye_batch");
+int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, int rs) { return batch_render("launch_eye_batch", false, n, subframes, r0, r1, rs); }
+int Context::launch_eye_batch_film(int n, const uint32_t* subframes, int r0, int r1, int rs) { return batch_render("launch_eye_batch_film", true, n, subframes, r0, r1, rs); }
+
+// `film`: the merge keeps the second moment and fills the buckets, whichever are on (k_film_merge_batch_stats); without it the launch
+// refuses while either is on, as it always has
+int Context::batch_render(const char* name, bool film, int n, const uint32_t* subframes, int r0, int r1, int rs) {
+    const std::string who(name);
+    int rc = uniform_merge_allowed(name);
     if (rc) return rc;
     if ((rc = film_ready())) return rc;
-    if (film_moments) {
+    if (!film && film_moments) {
         error = "launch_eye_batch: not with film moments enabled (spcbpt_set_film_moments): the batched merge takes up to 32 frames per pixel in one "
-                "pass and keeps no second moment (use spcbpt_launch per frame)";
+                "pass and keeps no second moment (use spcbpt_launch per frame, or spcbpt_launch_eye_batch_film)";
         return SPCBPT_ERR_STATE;
     }
-    if (film_buckets) {
+    if (!film && film_buckets) {
         error = "launch_eye_batch: not with the film's buckets on (spcbpt_set_film_buckets): the batched merge takes up to 32 frames per pixel in one "
-                "pass and fills no buckets (use spcbpt_launch per frame)";
+                "pass and fills no buckets (use spcbpt_launch per frame, or spcbpt_launch_eye_batch_film)";
         return SPCBPT_ERR_STATE;
     }
-    if (kp.lens_radius > 0.0f) { error = "launch_eye_batch: the batched eye kernel has no lens form (spcbpt_set_lens): use spcbpt_launch per frame, or set the lens radius to 0"; return SPCBPT_ERR_STATE; }
+    if (kp.lens_radius > 0.0f) { error = who + ": the batched eye kernel has no lens form (spcbpt_set_lens): use spcbpt_launch per frame, or set the lens radius to 0"; return SPCBPT_ERR_STATE; }
     if (!have_subspace) { error = "SPCBPT_eye needs a subspace tuple and a built sampler"; return SPCBPT_ERR_STATE; }
-    if (n < 1 || n > kMaxBatchFrames || !subframes) { error = "launch_eye_batch: 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
-    if (n > (int)built_sets.size()) { error = "launch_eye_batch: fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }
+    if (n < 1 || n > kMaxBatchFrames || !subframes) { error = who + ": 1..32 frames"; return SPCBPT_ERR_INVALID_ARG; }
+    if (n > (int)built_sets.size()) { error = who + ": fewer samplers have been built (and are still intact) than frames were asked for"; return SPCBPT_ERR_STATE; }
     // (SPCBPT_EYE_BATCH at spcbpt_create only sizes the ring of buffer sets so that batches, light passes ahead and builds do not
     // wait for each other; correctness rests on the per-set events and on `built_sets` naming intact samplers)
-    if (counting) { error = "launch_eye_batch: not with event counters enabled (count with spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
-    if (tree_has_direction) { error = "launch_eye_batch: the batched kernel caches vertex labels, which needs classifier trees without direction nodes (use spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
-    if (kp.width >= 65536u || kp.height >= 65536u) { error = "launch_eye_batch: image too large"; return SPCBPT_ERR_INVALID_ARG; }
+    if (counting) { error = who + ": not with event counters enabled (count with spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
+    if (tree_has_direction) { error = who + ": the batched kernel caches vertex labels, which needs classifier trees without direction nodes (use spcbpt_launch per frame)"; return SPCBPT_ERR_STATE; }
+    if (kp.width >= 65536u || kp.height >= 65536u) { error = who + ": image too large"; return SPCBPT_ERR_INVALID_ARG; }
     if ((rc = begin_render(r0, r1, rs))) return rc;
     kp.counters = nullptr;
     const size_t px = (size_t)kp.width * kp.height;
@@ -225,7 +234,30 @@ int Context::launch_eye_batch(int n, const uint32_t* subframes, int r0, int r1, 
     for (int k = 0; k < n; k++) { sets[batch[k]].render_event_of = eset; sets[batch[k]].render.set = true; }
     // the frames' merges, in frame order, after the previous launch's merge
     if ((rc = chain_wait())) return rc;
-    {   // ... as one pass over the pixels (kernels.hip: k_film_merge_batch -- the operations of n merges, per pixel in frame order)
+    if (film && (film_moments || film_buckets)) {
+        // ... as one pass that also does, per frame, what moments_step and buckets_step do in front of a single merge
+        // (kernels_merge_stats.hip: k_film_merge_batch_stats); the planes as those steps set them up
+        if (film_moments && !d_m2n) {
+            HIP_TRY(this, d_m2n.reserve(px * 4));
+            HIP_TRY(this, hipMemsetAsync(d_m2n, 0, px * 16, rstream));
+        }
+        if (film_buckets && (rc = ensure_buckets(rstream))) return rc;
+        MergeStatsParams mp;
+        memset(&mp, 0, sizeof(mp));
+        mp.width = kp.width; mp.height = kp.height;
+        mp.row_begin = kp.row_begin; mp.row_end = kp.row_end; mp.row_step = kp.row_step;
+        mp.frames = n; mp.buckets = film_buckets;
+        mp.accum = d_accum; mp.frame = kp.frame;
+        mp.m2n = film_moments ? d_m2n.p : nullptr; mp.planes = film_buckets ? d_buckets.p : nullptr;
+        for (int k = 0; k < n; k++) { mp.result[k] = d_result_b[rk][k]; mp.subframe[k] = subframes[k]; }
+        kp.subframe = subframes[n - 1];
+        kp.result = d_result_b[rk][0];
+        time_begin("film_merge_stats", rstream);
+        launch_film_merge_batch_stats(mp, rstream);
+        time_end();
+        HIP_TRY(this, hipGetLastError());
+    }
+    else {   // ... as one pass over the pixels (kernels.hip: k_film_merge_batch -- the operations of n merges, per pixel in frame order)
         MergeBatch mb = {};
         for (int k = 0; k < n; k++) { mb.result[k] = d_result_b[rk][k]; mb.subframe[k] = subframes[k]; }
         kp.subframe = subframes[n - 1];

@@ -31,7 +31,13 @@
 // --local-tone C [--local-detail D] [--local-cell S] [--local-range R]: that image -- after --bloom, if given -- goes through
 // spcbpt_local_tone (compress C in (0, 2], detail D, default 1, S = 4 .. 64 pixels per grid cell, default 16, R stops per bin, default 1)
 // and the local tone plane is what <out>_display.ppm shows; --local-tone alone implies the display pass with its defaults.
-//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]
+// --batch N (with --alg SPCBPT_eye; N = 2 .. 32): the uniform frames in groups of up to N -- the group's light passes as one launch
+// (spcbpt_launch_light_batch, the launch frames the per-frame loop uses), their sampler builds as one (spcbpt_build_sampler_batch) and one
+// spcbpt_launch_eye_batch_film, whose merge keeps the moments and the buckets -- so --target-error (asked after a group; --check-every
+// is rounded up to a multiple of N), --denoise-variance, --robust and the uniform phase of --adaptive run at the batched loop's rate.
+// The files are bit for bit those of the same command without --batch that renders as many frames.  Not with --features, --denoise,
+// --aperture or another algorithm: their per-frame launches have no batched form.
+//   spcbpt_render <file.scene> <data_root> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--batch N] [--out prefix]
 // Build: make -C tools   (links libspcbpt_hip.so)
 #include <algorithm>
 #include <chrono>
@@ -72,7 +78,7 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--batch N] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
@@ -94,6 +100,7 @@ int main(int argc, char** argv) {
     bool local_tone = false;      // --local-tone C: the shown image goes through spcbpt_local_tone (after spcbpt_bloom, if both)
     spcbpt_local_tone_params ltp;
     spcbpt_local_tone_default_params(&ltp);
+    int batch = 0;                // --batch N: the uniform frames in groups of up to N (one batched eye launch per group)
     float aperture = 0.0f, focus = 1.0f;   // --aperture R [--focus F]: a thin lens of radius R (world units) focused at depth F (1 = the lookat plane)
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
@@ -136,6 +143,7 @@ int main(int argc, char** argv) {
         else if (a == "--local-range" && i + 1 < argc) ltp.range = (float)atof(argv[++i]);
         else if (a == "--aperture" && i + 1 < argc) aperture = (float)atof(argv[++i]);
         else if (a == "--focus" && i + 1 < argc) focus = (float)atof(argv[++i]);
+        else if (a == "--batch" && i + 1 < argc) { batch = atoi(argv[++i]); if (batch == 0) batch = -1; }
         else if (a == "--out" && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "Unknown option '%s'\n", argv[i]); return 1; }
     }
@@ -147,6 +155,18 @@ int main(int argc, char** argv) {
     if (robust != 0 && (adaptive || robust < 3 || robust > 32)) {
         fprintf(stderr, "--robust K needs K in 3 .. 32 and no --adaptive\n");
         return 1;
+    }
+    if (batch != 0) {
+        if (batch < 2 || batch > 32) { fprintf(stderr, "--batch N needs N in 2 .. 32\n"); return 1; }
+        const char* why = alg != "SPCBPT_eye" ? "--alg other than SPCBPT_eye" : features ? "--features" : (denoise && !denoise_variance) ? "--denoise" : aperture != 0.0f ? "--aperture" : nullptr;
+        if (why) {
+            fprintf(stderr, "--batch: not with %s: its per-frame launches have no batched form (the batched eye kernel renders pinhole \"SPCBPT_eye\" frames, "
+                            "and the feature buffers of --features / --denoise are kept per frame)\n", why);
+            return 1;
+        }
+        char n[16];
+        snprintf(n, sizeof(n), "%d", batch);
+        setenv("SPCBPT_EYE_BATCH", n, 1);   // read by spcbpt_create: sizes the ring of sampler buffer sets for batches of N
     }
     spcbpt_scene_file* sf = nullptr;
     const std::string in(argv[1]);
@@ -201,6 +221,7 @@ int main(int argc, char** argv) {
     if (moments) CHECK(ctx, spcbpt_set_film_moments(ctx, 1));
     if (robust) CHECK(ctx, spcbpt_set_film_buckets(ctx, robust));
     if (check_every < 1) check_every = 1;
+    if (batch) check_every = (check_every + batch - 1) / batch * batch;   // the film error is asked after a group
     spcbpt_light_trace_params lt = {100000, 52, 1, 0, 0, 1};
     CHECK(ctx, spcbpt_set_light_trace(ctx, &lt));
     auto t0 = std::chrono::steady_clock::now();
@@ -217,7 +238,44 @@ int main(int argc, char** argv) {
     // --adaptive: the uniform frames the estimate needs, then only the tiles that are still above the target
     const int cap = adaptive ? (max_samples > 0 && max_samples < frames ? max_samples : frames) : 0;   // samples no tile passes
     const int uniform_frames = adaptive ? std::min(cap, std::max(min_samples, 2)) : frames;
-    for (int f = 0; f < uniform_frames; f++) {
+    if (batch) {   // the uniform frames in groups: light passes, sampler builds and the eye launch of a group as one launch each
+        // The loop of bench.py: the light passes run two groups ahead of the eye launch and the builds one -- a batched light pass is a
+        // thin grid meant to run BESIDE an eye kernel, and a group's builds run under the eye kernel of the group before.  Frame f keeps
+        // launch frame lt_frame + 1 + f, the one the loop below gives it.  (A run that stops at its target leaves the work ahead unused.)
+        CHECK(ctx, spcbpt_set_light_ahead(ctx, 1));   // (the batched light pass queues its passes for the builds)
+        const unsigned light0 = lt_frame + 1;
+        int lit = 0, built = 0;   // frames whose light pass has been launched / whose sampler has been built
+        auto light_next = [&]() {
+            const int g = std::min(batch, uniform_frames - lit);
+            if (g <= 0) return;
+            // (the first group has no eye kernel to run beside and everything waits for it: full-size single passes, which leave the
+            // same caches in the same queue, are done sooner than the thin grid of a batched pass)
+            if (lit == 0) for (int k = 0; k < g; k++) CHECK(ctx, spcbpt_launch(ctx, "light trace", light0 + (unsigned)k, 0, 0, 1));
+            else CHECK(ctx, spcbpt_launch_light_batch(ctx, light0 + (unsigned)lit, g));
+            lit += g;
+        };
+        auto build_next = [&]() {
+            const int g = std::min(batch, lit - built);
+            if (g > 0) { CHECK(ctx, spcbpt_build_sampler_batch(ctx, g)); built += g; }
+        };
+        light_next(); build_next(); light_next();
+        for (int f = 0; f < uniform_frames;) {
+            const int g = std::min(batch, uniform_frames - f);
+            uint32_t subframes[32];
+            for (int k = 0; k < g; k++) subframes[k] = (uint32_t)(f + k);
+            CHECK(ctx, spcbpt_launch_eye_batch_film(ctx, g, subframes, 0, height, 1));   // the samplers of the last g builds
+            build_next(); light_next();
+            if (denoise) for (int k = 0; k < g; k++) CHECK(ctx, spcbpt_launch_features(ctx, subframes[k], 0, height, 1));   // (--denoise-variance)
+            f += g;
+            if (!adaptive && target_error > 0.0 && f >= 2 && (f % check_every == 0 || f == frames)) {
+                CHECK(ctx, spcbpt_film_error(ctx, &reached));
+                if (reached.pixels > 0 && reached.mean <= target_error) { frames = f; break; }
+            }
+        }
+        CHECK(ctx, spcbpt_set_light_ahead(ctx, 0));   // (what follows -- the adaptive rounds -- builds from the latest pass again)
+        lt_frame += (unsigned)uniform_frames;
+    }
+    else for (int f = 0; f < uniform_frames; f++) {
         if (alg == "SPCBPT_eye" || lt_alg) {  // launchLVCTrace (optixPathTracer.cpp:515-522)
             CHECK(ctx, spcbpt_launch(ctx, "light trace", ++lt_frame, 0, 0, 1));
             CHECK(ctx, spcbpt_build_sampler(ctx));
