@@ -1237,6 +1237,19 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _source_index(source):
+    """The `source` of display / bloom / local_tone: a name of DISPLAY_SOURCES, or the number itself."""
+    return DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+
+
+def _image_arg(img, who):
+    """An image of the caller's as the *_image calls pass it on: contiguous float32 of shape (h, w, 4)."""
+    x = np.ascontiguousarray(img, dtype=np.float32)
+    if x.ndim != 3 or x.shape[-1] != 4:
+        raise SpcbptError(f"{who}: the image must be (h, w, 4)")
+    return x
+
+
 class Renderer:
     """One context per GPU (the `sutil::Scene` + `MyParams` pair of the reference driver)."""
 
@@ -1435,19 +1448,16 @@ class Renderer:
 
     # ---- display transform (spcbpt_display*): exposure, histogram auto-exposure, tone operators -- an RGBA8 plane of its own
     def display(self, source="film", **params):
-        """spcbpt_display: one of the context's linear images ("film", "denoised", "robust", "history") times 2^EV through a tone
-        operator into the display plane.  Parameters as display_params takes them: op="film" | "reinhard" | "aces" | "linear", ev=...,
-        auto=True (EV from the image's histogram, adapted on the device), histogram=True, key=..., ...  Read with read_display()."""
-        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
-        p = display_params(**params)
+        """spcbpt_display: one of the context's linear images -- every source of DISPLAY_SOURCES: "film", "denoised", "robust", "history",
+        the bloom plane ("bloom") or the local tone plane ("local") -- times 2^EV through a tone operator into the display plane.
+        Parameters as display_params takes them: op="film" | "reinhard" | "aces" | "linear", ev=..., auto=True (EV from the image's
+        histogram, adapted on the device), histogram=True, key=..., ...  Read with read_display()."""
+        src, p = _source_index(source), display_params(**params)
         self._chk(self.lib.spcbpt_display(self.h, src, C.byref(p)), "display")
 
     def display_image(self, img, **params):
         """spcbpt_display_image: the same pass on an (h, w, 4) float32 image of the caller's, any size."""
-        x = np.ascontiguousarray(img, dtype=np.float32)
-        if x.ndim != 3 or x.shape[-1] != 4:
-            raise SpcbptError("display_image: the image must be (h, w, 4)")
-        p = display_params(**params)
+        x, p = _image_arg(img, "display_image"), display_params(**params)
         self._chk(self.lib.spcbpt_display_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "display_image")
 
     def _display_size(self):
@@ -1476,53 +1486,47 @@ class Renderer:
 
     # ---- bloom (spcbpt_bloom*): a multi-scale glare ahead of the display transform -- a float4 plane of its own
     def bloom(self, source="film", **params):
-        """spcbpt_bloom: one of the context's linear images ("film", "denoised", "robust", "history") with the share `strength` of its
-        light above `threshold` spread over `levels` scales, into the bloom plane.  Parameters as bloom_params takes them.  Read with
-        read_bloom(); show with display("bloom", ...)."""
-        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
-        p = bloom_params(**params)
+        """spcbpt_bloom: one of the context's film-sized linear images -- "film", "denoised", "robust" or "history"; the "bloom" and
+        "local" planes of DISPLAY_SOURCES are no source of this stage -- with the share `strength` of its light above `threshold`
+        spread over `levels` scales, into the bloom plane.  Parameters as bloom_params takes them.  Read with read_bloom(); show with
+        display("bloom", ...)."""
+        src, p = _source_index(source), bloom_params(**params)
         self._chk(self.lib.spcbpt_bloom(self.h, src, C.byref(p)), "bloom")
 
     def bloom_image(self, img, **params):
         """spcbpt_bloom_image: the same stage on an (h, w, 4) float32 image of the caller's, any size."""
-        x = np.ascontiguousarray(img, dtype=np.float32)
-        if x.ndim != 3 or x.shape[-1] != 4:
-            raise SpcbptError("bloom_image: the image must be (h, w, 4)")
-        p = bloom_params(**params)
+        x, p = _image_arg(img, "bloom_image"), bloom_params(**params)
         self._chk(self.lib.spcbpt_bloom_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "bloom_image")
+
+    def _read_plane(self, fn, who):
+        """A float4 plane at a size of its own (spcbpt_read_bloom, spcbpt_read_local_tone): the size first, then the plane."""
+        w, h = C.c_int32(), C.c_int32()
+        self._chk(fn(self.h, None, C.byref(w), C.byref(h)), who)
+        out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
+        self._chk(fn(self.h, out.ctypes.data, None, None), who)
+        return out
 
     def read_bloom(self):
         """(h, w, 4) float32: the plane the last bloom() / bloom_image() wrote, at that call's image size."""
-        w, h = C.c_int32(), C.c_int32()
-        self._chk(self.lib.spcbpt_read_bloom(self.h, None, C.byref(w), C.byref(h)), "read_bloom")
-        out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
-        self._chk(self.lib.spcbpt_read_bloom(self.h, out.ctypes.data, None, None), "read_bloom")
-        return out
+        return self._read_plane(self.lib.spcbpt_read_bloom, "read_bloom")
 
     # ---- local tone mapping (spcbpt_local_tone*): base / detail through a bilateral grid -- a float4 plane of its own
     def local_tone(self, source="film", **params):
-        """spcbpt_local_tone: one of the context's linear images ("film", "denoised", "robust", "history") or the bloom plane ("bloom")
-        with its large-scale luminance range compressed by `compress` about `anchor` and its local contrast scaled by `detail`, into the
-        local tone plane.  Parameters as local_tone_params takes them.  Read with read_local_tone(); show with display("local", ...)."""
-        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
-        p = local_tone_params(**params)
+        """spcbpt_local_tone: one of the context's linear images -- "film", "denoised", "robust", "history" or the bloom plane ("bloom");
+        the "local" plane of DISPLAY_SOURCES is no source of this stage -- with its large-scale luminance range compressed by `compress`
+        about `anchor` and its local contrast scaled by `detail`, into the local tone plane.  Parameters as local_tone_params takes
+        them.  Read with read_local_tone(); show with display("local", ...)."""
+        src, p = _source_index(source), local_tone_params(**params)
         self._chk(self.lib.spcbpt_local_tone(self.h, src, C.byref(p)), "local_tone")
 
     def local_tone_image(self, img, **params):
         """spcbpt_local_tone_image: the same stage on an (h, w, 4) float32 image of the caller's, any size."""
-        x = np.ascontiguousarray(img, dtype=np.float32)
-        if x.ndim != 3 or x.shape[-1] != 4:
-            raise SpcbptError("local_tone_image: the image must be (h, w, 4)")
-        p = local_tone_params(**params)
+        x, p = _image_arg(img, "local_tone_image"), local_tone_params(**params)
         self._chk(self.lib.spcbpt_local_tone_image(self.h, _fp(x), x.shape[1], x.shape[0], C.byref(p)), "local_tone_image")
 
     def read_local_tone(self):
         """(h, w, 4) float32: the plane the last local_tone() / local_tone_image() wrote, at that call's image size."""
-        w, h = C.c_int32(), C.c_int32()
-        self._chk(self.lib.spcbpt_read_local_tone(self.h, None, C.byref(w), C.byref(h)), "read_local_tone")
-        out = np.zeros((int(h.value), int(w.value), 4), dtype=np.float32)
-        self._chk(self.lib.spcbpt_read_local_tone(self.h, out.ctypes.data, None, None), "read_local_tone")
-        return out
+        return self._read_plane(self.lib.spcbpt_read_local_tone, "read_local_tone")
 
     # ---- adaptive sampling (spcbpt_adaptive_*): tiles are 8x8 pixels of the whole film, numbered x-major
     def adaptive_begin(self, frames: int):

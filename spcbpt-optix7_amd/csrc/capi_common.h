@@ -3,10 +3,11 @@
 //   ctx_light.hip     Context: light passes (single / batched), the device sampler build (single / batched)
 //   ctx_exchange.hip  Context: the shards and imports of a sharded job (what libspcbpt_mgpu drives)
 //   ctx_render.hip    Context: eye / pt launches (single, deferred, batched), film merges
-//   ctx_features.hip  Context + extern "C": the first-hit feature pass and the a-trous denoiser
+//   ctx_features.hip  Context + extern "C": the first-hit feature pass, the a-trous denoiser and the driver the three denoisers share
 //   ctx_moments.hip   Context + extern "C": the film's second moment, the film error, the variance-guided denoiser
 //   ctx_buckets.hip   Context + extern "C": the bucket film and its median-of-means resolve
 //   ctx_display.hip   Context + extern "C": the display transform -- exposure, histogram auto-exposure, tone operators
+//                     ... and what the three image-space stages share: their sources, the scratch copy of a caller's image, the plane reader
 //   ctx_bloom.hip     Context + extern "C": the bloom stage -- a multi-scale glare ahead of the display transform
 //   ctx_local_tone.hip Context + extern "C": the local tone stage -- base / detail through a bilateral grid, ahead of the display transform
 //   ctx_history.hip   Context + extern "C": history capture, reprojection into the current view, resolve

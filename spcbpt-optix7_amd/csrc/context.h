@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <deque>
+#include <functional>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -16,6 +17,7 @@
 namespace spc {
 
 struct Preprocessor;
+struct DenoiseParams;   // kernels_denoise.h
 
 struct TimedSpan {
     std::string name;
@@ -349,6 +351,13 @@ struct Context {
     void next_render_stream();                 // consecutive render launches rotate through the render streams
     int chain_wait();    // `rstream` behind the last link of the film-merge chain
     int chain_end();     // ... and this launch as the chain's last link
+    template <class Run>
+    int chain_link(Run run) {   // one whole link: `run` queues its launches on `rstream`; a refusal of its own ends the call, not the link
+        next_render_stream();
+        if (int rc = chain_wait()) return rc;
+        if (int rc = run()) return rc;
+        return chain_end();
+    }
     int render_done(int s);   // the eye kernel just queued on `rstream` is the last reader of set s
     int finish_frame();
     // First-hit feature buffers and the denoiser's planes (ctx_features.hip): float4 per pixel each, allocated at the first feature
@@ -359,6 +368,12 @@ struct Context {
     bool have_features = false, have_denoised = false;                // ... since the last resize
     int launch_features(uint32_t subframe, int r0, int r1, int rs);
     int denoise(const spcbpt_denoise_params& p);
+    // The driver of the three denoisers (denoise, denoise_variance, history_denoise), after the preconditions of each.  denoise_begin: the
+    // parameter refusals under the caller's name, then the link begins.  denoise_run: the five planes, the span `who` -- `demodulate`
+    // (the caller's launch, from `input`), the a-trous passes of either form, k_remodulate --, have_denoised and the end of the link.
+    int denoise_begin(const char* who, const spcbpt_denoise_params& p);
+    int denoise_run(const char* who, const spcbpt_denoise_params& p, float sigma_c_default, const float* input, bool variance_guided,
+                    const std::function<void(const DenoiseParams&)>& demodulate);
     void free_features();
     // Second moment of the film (ctx_moments.hip; spcbpt_set_film_moments, off by default): one float4 per pixel (M2_r, M2_g, M2_b, n),
     // updated by k_film_moments in front of every film merge of finish_frame.  Allocated (zeroed) at the first merge after a resize
@@ -386,12 +401,37 @@ struct Context {
     int buckets_step();                    // finish_frame: the update of this launch's pixels, queued on `rstream` in front of the merge
     int robust_resolve(float strength);
     void free_buckets();
-    // Display transform (ctx_display.hip; spcbpt_display / spcbpt_display_image, opt-in): an RGBA8 plane of its own, the device record of
-    // kernels_display.h (histogram counters + adaptation state, 1 040 B) and, for spcbpt_display_image, a scratch copy of the caller's
-    // image.  Allocated at the first call, the plane and the scratch grow-only; spcbpt_resize frees all three (and with the record the
-    // previous EV).  A context that does not ask keeps its footprint, its launches and every plane's bits.
+    // The image-space stages (display, bloom, local tone) take one of the context's linear float4 images -- SPCBPT_DISPLAY_FILM .. _LOCAL,
+    // resolved by linear_image (ctx_display.hip), which words every refusal of a source under the stage's name `who` -- or an image of
+    // the caller's (spcbpt_*_image): caller_image refuses a null or mis-sized one, image_link is the link over a scratch copy of it.
+    // The ONE scratch copy serves the three stages: every use is a chain link, so its upload runs behind every kernel of the link
+    // before it, the call returns only when the upload is done, and a reserve that has to grow goes through hipFree, which waits for
+    // the device.  Grow-only (16 B per pixel of the largest image given), allocated at the first such call, freed by spcbpt_resize.
+    struct LinearImage {
+        const float* p = nullptr;
+        int width = 0, height = 0;
+    };
+    struct Plane {   // a float4 plane at the size of the image it was made from
+        bool have = false;           // ... since the last resize
+        int width = 0, height = 0;
+    };
+    DevBuf<float> d_stage_src;
+    int linear_image(const char* who, int source, int last_source, LinearImage* out);
+    int caller_image(const char* who, const float* rgba, int width, int height);
+    int stage_upload(const float* rgba, int width, int height);   // inside a link: into d_stage_src on `rstream`, and waited for
+    int read_plane(const char* stage, const Plane& b, const float* plane, float* rgba, int* width, int* height);   // spcbpt_read_bloom / _local_tone
+    template <class Run>
+    int image_link(const float* rgba, int width, int height, Run run) {
+        return chain_link([&]() -> int {
+            if (int rc = stage_upload(rgba, width, height)) return rc;
+            return run(d_stage_src.p);
+        });
+    }
+    // Display transform (ctx_display.hip; spcbpt_display / spcbpt_display_image, opt-in): an RGBA8 plane of its own and the device record
+    // of kernels_display.h (histogram counters + adaptation state, 1 040 B).  Allocated at the first call, the plane grow-only;
+    // spcbpt_resize frees both (and with the record the previous EV).  A context that does not ask keeps its footprint, its launches and
+    // every plane's bits.
     DevBuf<uint32_t> d_display_frame, d_display_state;
-    DevBuf<float> d_display_src;
     struct Display {
         bool have = false, have_hist = false, auto_ev = false;   // of the last call
         int width = 0, height = 0;                               // ... the size of the image it showed
@@ -401,30 +441,22 @@ struct Context {
     int display_image(const float* rgba, int width, int height, const spcbpt_display_params& p);
     int display_run(const float* src, int width, int height, const spcbpt_display_params& p);   // the launches, on `rstream` inside a chain link
     int display_reset();
-    void free_display();
+    void free_display();   // ... and the stages' scratch copy
     // Bloom (ctx_bloom.hip; spcbpt_bloom / spcbpt_bloom_image, opt-in): a float4 plane of its own at the size of the image it was made
-    // from, the pyramid scratch (float4 per texel of the levels 1 .. L: about a third of the image) and, for spcbpt_bloom_image, a scratch
-    // copy of the caller's image.  Allocated at the first call, grow-only; spcbpt_resize frees all three.  A context that does not ask
-    // keeps its footprint, its launches and every plane's bits.
-    DevBuf<float> d_bloom, d_bloom_pyr, d_bloom_src;
-    struct Bloom {
-        bool have = false;         // a bloom plane since the last resize
-        int width = 0, height = 0; // ... its size
-    } bloom_last;
+    // from and the pyramid scratch (float4 per texel of the levels 1 .. L: about a third of the image).  Allocated at the first call,
+    // grow-only; spcbpt_resize frees both.  A context that does not ask keeps its footprint, its launches and every plane's bits.
+    DevBuf<float> d_bloom, d_bloom_pyr;
+    Plane bloom_last;
     int bloom(int source, const spcbpt_bloom_params& p);
     int bloom_image(const float* rgba, int width, int height, const spcbpt_bloom_params& p);
     int bloom_run(const float* src, int width, int height, const spcbpt_bloom_params& p);   // the launches, on `rstream` inside a chain link
     void free_bloom();
     // Local tone mapping (ctx_local_tone.hip; spcbpt_local_tone / spcbpt_local_tone_image, opt-in): a float4 plane of its own at the size
-    // of the image it was made from, the two grid buffers the gather and the blur passes go back and forth between (two floats per node,
-    // (W / cell + 2)(H / cell + 2)(32 / range + 2) nodes: 2.3 MB each at 1920 x 1080 with the defaults) and, for spcbpt_local_tone_image,
-    // a scratch copy of the caller's image.  Allocated at the first call, grow-only; spcbpt_resize frees all four.  A context that does
-    // not ask keeps its footprint, its launches and every plane's bits.
-    DevBuf<float> d_local, d_local_grid[2], d_local_src;
-    struct LocalTone {
-        bool have = false;         // a local tone plane since the last resize
-        int width = 0, height = 0; // ... its size
-    } local_last;
+    // of the image it was made from and the two grid buffers the gather and the blur passes go back and forth between (two floats per
+    // node, (W / cell + 2)(H / cell + 2)(32 / range + 2) nodes: 2.3 MB each at 1920 x 1080 with the defaults).  Allocated at the first
+    // call, grow-only; spcbpt_resize frees all three.  A context that does not ask keeps its footprint, its launches and every plane's bits.
+    DevBuf<float> d_local, d_local_grid[2];
+    Plane local_last;
     int local_tone(int source, const spcbpt_local_tone_params& p);
     int local_tone_image(const float* rgba, int width, int height, const spcbpt_local_tone_params& p);
     int local_tone_run(const float* src, int width, int height, const spcbpt_local_tone_params& p);   // the launches, on `rstream` inside a chain link

@@ -9,8 +9,8 @@ using namespace spc;
 namespace spc {
 
 void Context::free_bloom() {
-    d_bloom.release(); d_bloom_pyr.release(); d_bloom_src.release();
-    bloom_last = Bloom();
+    d_bloom.release(); d_bloom_pyr.release();
+    bloom_last = Plane();
 }
 
 static const char* bloom_check(const spcbpt_bloom_params& p) { return bloom_params_error(p.levels, p.strength, p.spread, p.threshold, p.clamp); }
@@ -45,44 +45,20 @@ int Context::bloom_run(const float* src, int width, int height, const spcbpt_blo
 }
 
 // spcbpt_bloom: a link of the film-merge chain like Context::display -- it sees every merge, denoise and resolve queued before it, and
-// nothing queued later rewrites its source under it.  Writes its own plane and pyramid only.  The refusals are spcbpt_display's.
+// nothing queued later rewrites its source under it.  Writes its own plane and pyramid only.  The sources and their refusals are
+// Context::linear_image's, up to the resolved history image.
 int Context::bloom(int source, const spcbpt_bloom_params& p) {
     if (const char* bad = bloom_check(p)) { error = bad; return SPCBPT_ERR_INVALID_ARG; }
-    if (source < SPCBPT_DISPLAY_FILM || source > SPCBPT_DISPLAY_HISTORY) { error = "bloom: source must be 0 (film), 1 (denoised), 2 (robust) or 3 (history)"; return SPCBPT_ERR_INVALID_ARG; }
-    if (deferred.active) { error = "bloom: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (!d_accum) { error = "bloom before spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    const float* src = d_accum;
-    if (source == SPCBPT_DISPLAY_DENOISED) {
-        if (!have_denoised) { error = "bloom: no denoised image: spcbpt_denoise / spcbpt_denoise_variance / spcbpt_history_denoise since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-        src = d_denoised;
-    } else if (source == SPCBPT_DISPLAY_ROBUST) {
-        if (!film_buckets) { error = "bloom: no robust image: the film's buckets are off (spcbpt_set_film_buckets, then spcbpt_robust_resolve)"; return SPCBPT_ERR_STATE; }
-        if (!have_robust) { error = "bloom: no robust image: no spcbpt_robust_resolve since the film's buckets were last set up"; return SPCBPT_ERR_STATE; }
-        src = d_robust;
-    } else if (source == SPCBPT_DISPLAY_HISTORY) {
-        if (!have_resolved) { error = "bloom: no resolved history image: spcbpt_history_resolve since the last spcbpt_resize / spcbpt_history_reset"; return SPCBPT_ERR_STATE; }
-        src = d_resolved;
-    }
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    if (int rc = bloom_run(src, (int)kp.width, (int)kp.height, p)) return rc;
-    return chain_end();
+    LinearImage im;
+    if (int rc = linear_image("bloom", source, SPCBPT_DISPLAY_HISTORY, &im)) return rc;
+    return chain_link([&] { return bloom_run(im.p, im.width, im.height, p); });
 }
 
-// spcbpt_bloom_image: the same link over a scratch copy of the caller's image, uploaded behind the chain and waited for, so that the
-// caller's image may go when the call returns (Context::display_image's way).
+// spcbpt_bloom_image: the same link over the scratch copy of the caller's image (Context::image_link).
 int Context::bloom_image(const float* rgba, int width, int height, const spcbpt_bloom_params& p) {
     if (const char* bad = bloom_check(p)) { error = bad; return SPCBPT_ERR_INVALID_ARG; }
-    if (!rgba) { error = "null pointer"; return SPCBPT_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) { error = "bloom_image: the image must hold 1 .. 2^28 pixels"; return SPCBPT_ERR_INVALID_ARG; }
-    const size_t px = (size_t)width * height;
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    HIP_TRY(this, d_bloom_src.reserve(px * 4));
-    HIP_TRY(this, hipMemcpyAsync(d_bloom_src, rgba, px * 16, hipMemcpyHostToDevice, rstream));
-    HIP_TRY(this, hipStreamSynchronize(rstream));
-    if (int rc = bloom_run(d_bloom_src, width, height, p)) return rc;
-    return chain_end();
+    if (int rc = caller_image("bloom", rgba, width, height)) return rc;
+    return image_link(rgba, width, height, [&](const float* src) { return bloom_run(src, width, height, p); });
 }
 
 }  // namespace spc
@@ -103,14 +79,7 @@ int spcbpt_bloom_image(spcbpt_ctx* c, const float* rgba, int width, int height, 
 
 int spcbpt_read_bloom(spcbpt_ctx* c, float* rgba, int* width, int* height) {
     CTX_CHECK(c);
-    const Context::Bloom& b = c->bloom_last;
-    if (!b.have) { c->error = "read_bloom: no spcbpt_bloom / spcbpt_bloom_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (c->sync_all()) return SPCBPT_ERR_HIP;
-    if (int rc = c->check_diag()) return rc;
-    if (width) *width = b.width;
-    if (height) *height = b.height;
-    if (rgba) HIP_TRY(c, hipMemcpy(rgba, c->d_bloom, (size_t)b.width * b.height * 16, hipMemcpyDeviceToHost));
-    return SPCBPT_OK;
+    return c->read_plane("bloom", c->bloom_last, c->d_bloom, rgba, width, height);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // Context: the display transform (kernels_display.hip) -- exposure, histogram auto-exposure and the tone operators over one of the
-// context's linear images or an image of the caller's, into an RGBA8 plane of its own
+// context's linear images or an image of the caller's, into an RGBA8 plane of its own -- and what the bloom and the local tone stage
+// share with it: the sources (Context::linear_image) and the scratch copy of a caller's image
 // (part of the C ABI library: see capi_common.h for the map of its translation units)
 #include "capi_common.h"
 #include "kernels_display.h"
@@ -9,7 +10,7 @@ using namespace spc;
 namespace spc {
 
 void Context::free_display() {
-    d_display_frame.release(); d_display_state.release(); d_display_src.release();
+    d_display_frame.release(); d_display_state.release(); d_stage_src.release();
     display_last = Display();
 }
 
@@ -49,59 +50,77 @@ int Context::display_run(const float* src, int width, int height, const spcbpt_d
     return 0;
 }
 
+// A source of the image-space stages as a pointer and a size, or the stage's refusal under its name `who`: the range (a stage takes the
+// sources up to its `last_source`), the deferred frame, the film for the four sources of its size, the plane itself.  The bloom and the
+// local tone plane come at the size of the image they were made from and need no film (spcbpt_bloom_image needs none).
+int Context::linear_image(const char* who, int source, int last_source, LinearImage* out) {
+    struct Row { int source; const char* name; bool have; const float* p; const Plane* size; const char* missing; };   // size: null = the film's
+    const Row rows[] = {
+        {SPCBPT_DISPLAY_FILM, "film", true, d_accum, nullptr, ""},
+        {SPCBPT_DISPLAY_DENOISED, "denoised", have_denoised, d_denoised, nullptr, "no denoised image: spcbpt_denoise / spcbpt_denoise_variance / spcbpt_history_denoise since the last spcbpt_resize"},
+        {SPCBPT_DISPLAY_ROBUST, "robust", film_buckets && have_robust, d_robust, nullptr,
+         !film_buckets ? "no robust image: the film's buckets are off (spcbpt_set_film_buckets, then spcbpt_robust_resolve)" : "no robust image: no spcbpt_robust_resolve since the film's buckets were last set up"},
+        {SPCBPT_DISPLAY_HISTORY, "history", have_resolved, d_resolved, nullptr, "no resolved history image: spcbpt_history_resolve since the last spcbpt_resize / spcbpt_history_reset"},
+        {SPCBPT_DISPLAY_BLOOM, "bloom", bloom_last.have, d_bloom, &bloom_last, "no bloom plane: spcbpt_bloom / spcbpt_bloom_image since the last spcbpt_resize"},
+        {SPCBPT_DISPLAY_LOCAL, "local", local_last.have, d_local, &local_last, "no local tone plane: spcbpt_local_tone / spcbpt_local_tone_image since the last spcbpt_resize"},
+    };
+    static_assert(SPCBPT_DISPLAY_FILM == 0 && SPCBPT_DISPLAY_LOCAL == sizeof(rows) / sizeof(rows[0]) - 1, "rows[source] is the row of `source`");
+    const std::string stage = who;
+    if (source < 0 || source > last_source) {
+        error = stage + ": source must be ";   // "0 (film), 1 (denoised), 2 (robust) or 3 (history)"
+        for (int k = 0; k <= last_source; k++) error += (k == 0 ? "" : k == last_source ? " or " : ", ") + std::to_string(rows[k].source) + " (" + rows[k].name + ")";
+        return SPCBPT_ERR_INVALID_ARG;
+    }
+    if (deferred.active) { error = stage + ": a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
+    const Row& r = rows[source];
+    if (!r.size && !d_accum) { error = stage + " before spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (!r.have) { error = stage + ": " + r.missing; return SPCBPT_ERR_STATE; }
+    *out = r.size ? LinearImage{r.p, r.size->width, r.size->height} : LinearImage{r.p, (int)kp.width, (int)kp.height};
+    return 0;
+}
+
+// spcbpt_*_image: the caller's image is there and holds 1 .. 2^28 pixels ...
+int Context::caller_image(const char* who, const float* rgba, int width, int height) {
+    if (!rgba) { error = "null pointer"; return SPCBPT_ERR_INVALID_ARG; }
+    if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) { error = std::string(who) + "_image: the image must hold 1 .. 2^28 pixels"; return SPCBPT_ERR_INVALID_ARG; }
+    return 0;
+}
+
+// ... and its scratch copy (Context::image_link).  The upload is queued behind the chain (the link before may still read the scratch)
+// and waited for, so that the caller's image may go when the call returns.
+int Context::stage_upload(const float* rgba, int width, int height) {
+    const size_t px = (size_t)width * height;
+    HIP_TRY(this, d_stage_src.reserve(px * 4));
+    HIP_TRY(this, hipMemcpyAsync(d_stage_src, rgba, px * 16, hipMemcpyHostToDevice, rstream));
+    HIP_TRY(this, hipStreamSynchronize(rstream));
+    return 0;
+}
+
+// spcbpt_read_bloom / spcbpt_read_local_tone: the float4 plane of `stage` and its size, each optional.
+int Context::read_plane(const char* stage, const Plane& b, const float* plane, float* rgba, int* width, int* height) {
+    if (!b.have) { error = std::string("read_") + stage + ": no spcbpt_" + stage + " / spcbpt_" + stage + "_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (sync_all()) return SPCBPT_ERR_HIP;
+    if (int rc = check_diag()) return rc;
+    if (width) *width = b.width;
+    if (height) *height = b.height;
+    if (rgba) HIP_TRY(this, hipMemcpy(rgba, plane, (size_t)b.width * b.height * 16, hipMemcpyDeviceToHost));
+    return SPCBPT_OK;
+}
+
 // spcbpt_display: a link of the film-merge chain like Context::robust_resolve -- it sees every merge, denoise and resolve queued before
 // it, and nothing queued later rewrites its source under it.  Writes its own plane and record only.
 int Context::display(int source, const spcbpt_display_params& p) {
     if (const char* bad = display_check(p)) { error = bad; return SPCBPT_ERR_INVALID_ARG; }
-    if (source < SPCBPT_DISPLAY_FILM || source > SPCBPT_DISPLAY_LOCAL) { error = "display: source must be 0 (film), 1 (denoised), 2 (robust), 3 (history), 4 (bloom) or 5 (local)"; return SPCBPT_ERR_INVALID_ARG; }
-    if (deferred.active) { error = "display: a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (source == SPCBPT_DISPLAY_BLOOM) {   // the bloom plane, at the size of the image it was made from (spcbpt_bloom_image needs no film)
-        if (!bloom_last.have) { error = "display: no bloom plane: spcbpt_bloom / spcbpt_bloom_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-        next_render_stream();
-        if (int rc = chain_wait()) return rc;
-        if (int rc = display_run(d_bloom, bloom_last.width, bloom_last.height, p)) return rc;
-        return chain_end();
-    }
-    if (source == SPCBPT_DISPLAY_LOCAL) {   // the local tone plane, likewise at its own size
-        if (!local_last.have) { error = "display: no local tone plane: spcbpt_local_tone / spcbpt_local_tone_image since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-        next_render_stream();
-        if (int rc = chain_wait()) return rc;
-        if (int rc = display_run(d_local, local_last.width, local_last.height, p)) return rc;
-        return chain_end();
-    }
-    if (!d_accum) { error = "display before spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    const float* src = d_accum;
-    if (source == SPCBPT_DISPLAY_DENOISED) {
-        if (!have_denoised) { error = "display: no denoised image: spcbpt_denoise / spcbpt_denoise_variance / spcbpt_history_denoise since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-        src = d_denoised;
-    } else if (source == SPCBPT_DISPLAY_ROBUST) {
-        if (!film_buckets) { error = "display: no robust image: the film's buckets are off (spcbpt_set_film_buckets, then spcbpt_robust_resolve)"; return SPCBPT_ERR_STATE; }
-        if (!have_robust) { error = "display: no robust image: no spcbpt_robust_resolve since the film's buckets were last set up"; return SPCBPT_ERR_STATE; }
-        src = d_robust;
-    } else if (source == SPCBPT_DISPLAY_HISTORY) {
-        if (!have_resolved) { error = "display: no resolved history image: spcbpt_history_resolve since the last spcbpt_resize / spcbpt_history_reset"; return SPCBPT_ERR_STATE; }
-        src = d_resolved;
-    }
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    if (int rc = display_run(src, (int)kp.width, (int)kp.height, p)) return rc;
-    return chain_end();
+    LinearImage im;
+    if (int rc = linear_image("display", source, SPCBPT_DISPLAY_LOCAL, &im)) return rc;
+    return chain_link([&] { return display_run(im.p, im.width, im.height, p); });
 }
 
-// spcbpt_display_image: the same link over a scratch copy of the caller's image.  The upload is queued behind the chain (an earlier
-// call may still read the scratch) and waited for, so that the caller's image may go when the call returns; nothing waits for the EV.
+// spcbpt_display_image: the same link over the scratch copy of the caller's image; nothing waits for the EV.
 int Context::display_image(const float* rgba, int width, int height, const spcbpt_display_params& p) {
     if (const char* bad = display_check(p)) { error = bad; return SPCBPT_ERR_INVALID_ARG; }
-    if (!rgba) { error = "null pointer"; return SPCBPT_ERR_INVALID_ARG; }
-    if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) { error = "display_image: the image must hold 1 .. 2^28 pixels"; return SPCBPT_ERR_INVALID_ARG; }
-    const size_t px = (size_t)width * height;
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    HIP_TRY(this, d_display_src.reserve(px * 4));
-    HIP_TRY(this, hipMemcpyAsync(d_display_src, rgba, px * 16, hipMemcpyHostToDevice, rstream));
-    HIP_TRY(this, hipStreamSynchronize(rstream));
-    if (int rc = display_run(d_display_src, width, height, p)) return rc;
-    return chain_end();
+    if (int rc = caller_image("display", rgba, width, height)) return rc;
+    return image_link(rgba, width, height, [&](const float* src) { return display_run(src, width, height, p); });
 }
 
 // spcbpt_display_reset: the record's adaptation words to zero, as a chain link: behind the display calls already queued.

@@ -55,20 +55,25 @@ int Context::launch_features(uint32_t subframe, int r0, int r1, int rs) {
     return chain_end();
 }
 
-// spcbpt_denoise: demodulate -> `iterations` a-trous passes between two planes -> remodulate + tone map, as one "denoise" span.
-int Context::denoise(const spcbpt_denoise_params& dp) {
-    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
-    if (!d_accum) { error = "denoise before spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (!have_features) { error = "denoise needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (dp.iterations < 1 || dp.iterations > kDenoiseMaxIterations) { error = "denoise: iterations must be in 1..8"; return SPCBPT_ERR_INVALID_ARG; }
-    if (!(dp.sigma_c == dp.sigma_c) || !(dp.sigma_n == dp.sigma_n) || !(dp.sigma_x == dp.sigma_x)) { error = "denoise: a sigma is not a number"; return SPCBPT_ERR_INVALID_ARG; }
+// What the three denoisers share.  denoise_begin: the refusals of `iterations` and of a NaN sigma under the caller's name `who`, then the
+// link begins -- what the caller queues on `rstream` from here on (denoise_variance: its zero moments) runs in front of the filter.
+int Context::denoise_begin(const char* who, const spcbpt_denoise_params& dp) {
+    if (dp.iterations < 1 || dp.iterations > kDenoiseMaxIterations) { error = std::string(who) + ": iterations must be in 1..8"; return SPCBPT_ERR_INVALID_ARG; }
+    if (!(dp.sigma_c == dp.sigma_c) || !(dp.sigma_n == dp.sigma_n) || !(dp.sigma_x == dp.sigma_x)) { error = std::string(who) + ": a sigma is not a number"; return SPCBPT_ERR_INVALID_ARG; }
+    next_render_stream();
+    return chain_wait();
+}
+
+// denoise_run: the sigmas (<= 0: the defaults, the colour / variance one the caller's), the five planes at the first call after a resize,
+// and the launches as one span `who`: the caller's demodulate of `input` -> `iterations` a-trous passes between the two planes, plain
+// or variance-guided -> remodulate + tone map.  Ends the link.
+int Context::denoise_run(const char* who, const spcbpt_denoise_params& dp, float sigma_c_default, const float* input, bool variance_guided,
+                         const std::function<void(const DenoiseParams&)>& demodulate) {
     const float ext[3] = {bbox_hi[0] - bbox_lo[0], bbox_hi[1] - bbox_lo[1], bbox_hi[2] - bbox_lo[2]};
     const float diag = sqrtf(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]);
-    const float sigma_c = dp.sigma_c > 0.0f ? dp.sigma_c : SPCBPT_DENOISE_SIGMA_C;
+    const float sigma_c = dp.sigma_c > 0.0f ? dp.sigma_c : sigma_c_default;
     const float sigma_n = dp.sigma_n > 0.0f ? dp.sigma_n : SPCBPT_DENOISE_SIGMA_N;
     const float sigma_x = dp.sigma_x > 0.0f ? dp.sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
     const size_t px = (size_t)kp.width * kp.height;
     if (!d_denoised) {
         HIP_TRY(this, d_dn_position.reserve(px * 4));
@@ -81,16 +86,28 @@ int Context::denoise(const spcbpt_denoise_params& dp) {
     memset(&q, 0, sizeof(q));
     memcpy(q.U, kp.U, 12); memcpy(q.V, kp.V, 12); memcpy(q.W, kp.W, 12);
     q.width = kp.width; q.height = kp.height;
-    q.accum = d_accum; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
+    q.accum = input; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
     q.position = d_dn_position; q.ping = d_dn_ping; q.pong = d_dn_pong; q.denoised = d_denoised; q.frame = d_denoised_frame;
-    time_begin("denoise", rstream);
-    launch_demodulate(q, rstream);
-    for (int i = 0; i < dp.iterations; i++) launch_atrous(q, atrous_step(i, sigma_c, sigma_n, sigma_x), (i & 1) == 0, rstream);
+    time_begin(who, rstream);
+    demodulate(q);
+    for (int i = 0; i < dp.iterations; i++) {
+        if (variance_guided) launch_atrous_var(q, atrous_var_step(i, sigma_c, sigma_n, sigma_x), (i & 1) == 0, rstream);
+        else launch_atrous(q, atrous_step(i, sigma_c, sigma_n, sigma_x), (i & 1) == 0, rstream);
+    }
     launch_remodulate(q, (dp.iterations & 1) != 0, rstream);
     time_end();
     HIP_TRY(this, hipGetLastError());
     have_denoised = true;
     return chain_end();
+}
+
+// spcbpt_denoise: the plain filter on the film, as one "denoise" span.
+int Context::denoise(const spcbpt_denoise_params& dp) {
+    if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
+    if (!d_accum) { error = "denoise before spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (!have_features) { error = "denoise needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    if (int rc = denoise_begin("denoise", dp)) return rc;
+    return denoise_run("denoise", dp, SPCBPT_DENOISE_SIGMA_C, d_accum, false, [&](const DenoiseParams& q) { launch_demodulate(q, rstream); });
 }
 
 }  // namespace spc

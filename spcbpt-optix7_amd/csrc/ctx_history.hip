@@ -143,43 +143,14 @@ int Context::history_resolve(uint32_t frames) {
     return chain_end();
 }
 
-// spcbpt_history_denoise: Context::denoise_variance's launches from the resolved image and its variance -- k_demodulate_resolved, the
+// spcbpt_history_denoise: Context::denoise_run (ctx_features.hip) from the resolved image and its variance -- k_demodulate_resolved, the
 // variance-guided a-trous passes, k_remodulate -- as one "history_denoise" span.  Writes the denoiser's planes only.
 int Context::history_denoise(const spcbpt_denoise_params& dp) {
     if (int rc = history_ready("history_denoise", true)) return rc;
     if (!have_resolved) { error = "history_denoise needs a resolved image: spcbpt_history_resolve since the last spcbpt_resize / spcbpt_history_reset"; return SPCBPT_ERR_STATE; }
     if (!have_resolved_var) { error = "history_denoise: the resolved image has no variance -- the moments were off at the capture or resolve (spcbpt_set_film_moments(ctx, 1) before both)"; return SPCBPT_ERR_STATE; }
-    if (dp.iterations < 1 || dp.iterations > kDenoiseMaxIterations) { error = "history_denoise: iterations must be in 1..8"; return SPCBPT_ERR_INVALID_ARG; }
-    if (!(dp.sigma_c == dp.sigma_c) || !(dp.sigma_n == dp.sigma_n) || !(dp.sigma_x == dp.sigma_x)) { error = "history_denoise: a sigma is not a number"; return SPCBPT_ERR_INVALID_ARG; }
-    const float ext[3] = {bbox_hi[0] - bbox_lo[0], bbox_hi[1] - bbox_lo[1], bbox_hi[2] - bbox_lo[2]};
-    const float diag = sqrtf(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]);
-    const float sigma_v = dp.sigma_c > 0.0f ? dp.sigma_c : SPCBPT_DENOISE_SIGMA_V;
-    const float sigma_n = dp.sigma_n > 0.0f ? dp.sigma_n : SPCBPT_DENOISE_SIGMA_N;
-    const float sigma_x = dp.sigma_x > 0.0f ? dp.sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    const size_t px = (size_t)kp.width * kp.height;
-    if (!d_denoised) {
-        HIP_TRY(this, d_dn_position.reserve(px * 4));
-        HIP_TRY(this, d_dn_ping.reserve(px * 4));
-        HIP_TRY(this, d_dn_pong.reserve(px * 4));
-        HIP_TRY(this, d_denoised_frame.reserve(px));
-        HIP_TRY(this, d_denoised.reserve(px * 4));
-    }
-    DenoiseParams q;
-    memset(&q, 0, sizeof(q));
-    memcpy(q.U, kp.U, 12); memcpy(q.V, kp.V, 12); memcpy(q.W, kp.W, 12);
-    q.width = kp.width; q.height = kp.height;
-    q.accum = d_resolved; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
-    q.position = d_dn_position; q.ping = d_dn_ping; q.pong = d_dn_pong; q.denoised = d_denoised; q.frame = d_denoised_frame;
-    time_begin("history_denoise", rstream);
-    launch_demodulate_resolved(q, d_resolved_var, rstream);
-    for (int i = 0; i < dp.iterations; i++) launch_atrous_var(q, atrous_var_step(i, sigma_v, sigma_n, sigma_x), (i & 1) == 0, rstream);
-    launch_remodulate(q, (dp.iterations & 1) != 0, rstream);
-    time_end();
-    HIP_TRY(this, hipGetLastError());
-    have_denoised = true;
-    return chain_end();
+    if (int rc = denoise_begin("history_denoise", dp)) return rc;
+    return denoise_run("history_denoise", dp, SPCBPT_DENOISE_SIGMA_V, d_resolved, true, [&](const DenoiseParams& q) { launch_demodulate_resolved(q, d_resolved_var, rstream); });
 }
 
 }  // namespace spc

@@ -65,48 +65,20 @@ int Context::film_error(spcbpt_film_error_stats* out) {
     return check_diag();
 }
 
-// spcbpt_denoise_variance: demodulate (with the variance start values) -> `iterations` variance-guided a-trous passes between the
-// denoiser's two planes -> k_remodulate, as one "denoise_variance" span.  A link of the film-merge chain like Context::denoise.
+// spcbpt_denoise_variance: Context::denoise_run (ctx_features.hip) from k_demodulate_var's start values -- the film and its moments --
+// through the variance-guided a-trous passes, as one "denoise_variance" span.  A link of the film-merge chain like Context::denoise.
 int Context::denoise_variance(const spcbpt_denoise_params& dp) {
     if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (!d_accum) { error = "denoise_variance before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!film_moments) { error = "denoise_variance needs the film's moments: spcbpt_set_film_moments(ctx, 1) before the frames are rendered"; return SPCBPT_ERR_STATE; }
     if (!have_features) { error = "denoise_variance needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
-    if (dp.iterations < 1 || dp.iterations > kDenoiseMaxIterations) { error = "denoise_variance: iterations must be in 1..8"; return SPCBPT_ERR_INVALID_ARG; }
-    if (!(dp.sigma_c == dp.sigma_c) || !(dp.sigma_n == dp.sigma_n) || !(dp.sigma_x == dp.sigma_x)) { error = "denoise_variance: a sigma is not a number"; return SPCBPT_ERR_INVALID_ARG; }
-    const float ext[3] = {bbox_hi[0] - bbox_lo[0], bbox_hi[1] - bbox_lo[1], bbox_hi[2] - bbox_lo[2]};
-    const float diag = sqrtf(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]);
-    const float sigma_v = dp.sigma_c > 0.0f ? dp.sigma_c : SPCBPT_DENOISE_SIGMA_V;
-    const float sigma_n = dp.sigma_n > 0.0f ? dp.sigma_n : SPCBPT_DENOISE_SIGMA_N;
-    const float sigma_x = dp.sigma_x > 0.0f ? dp.sigma_x : SPCBPT_DENOISE_SIGMA_X_FRACTION * (diag > 0.0f ? diag : 1.0f);
-    next_render_stream();
-    if (int rc = chain_wait()) return rc;
-    const size_t px = (size_t)kp.width * kp.height;
+    if (int rc = denoise_begin("denoise_variance", dp)) return rc;
     if (!d_m2n) {   // moments on, but no merge since the last resize: every pixel has n = 0
+        const size_t px = (size_t)kp.width * kp.height;
         HIP_TRY(this, d_m2n.reserve(px * 4));
         HIP_TRY(this, hipMemsetAsync(d_m2n, 0, px * 16, rstream));
     }
-    if (!d_denoised) {
-        HIP_TRY(this, d_dn_position.reserve(px * 4));
-        HIP_TRY(this, d_dn_ping.reserve(px * 4));
-        HIP_TRY(this, d_dn_pong.reserve(px * 4));
-        HIP_TRY(this, d_denoised_frame.reserve(px));
-        HIP_TRY(this, d_denoised.reserve(px * 4));
-    }
-    DenoiseParams q;
-    memset(&q, 0, sizeof(q));
-    memcpy(q.U, kp.U, 12); memcpy(q.V, kp.V, 12); memcpy(q.W, kp.W, 12);
-    q.width = kp.width; q.height = kp.height;
-    q.accum = d_accum; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
-    q.position = d_dn_position; q.ping = d_dn_ping; q.pong = d_dn_pong; q.denoised = d_denoised; q.frame = d_denoised_frame;
-    time_begin("denoise_variance", rstream);
-    launch_demodulate_var(q, d_m2n, rstream);
-    for (int i = 0; i < dp.iterations; i++) launch_atrous_var(q, atrous_var_step(i, sigma_v, sigma_n, sigma_x), (i & 1) == 0, rstream);
-    launch_remodulate(q, (dp.iterations & 1) != 0, rstream);
-    time_end();
-    HIP_TRY(this, hipGetLastError());
-    have_denoised = true;
-    return chain_end();
+    return denoise_run("denoise_variance", dp, SPCBPT_DENOISE_SIGMA_V, d_accum, true, [&](const DenoiseParams& q) { launch_demodulate_var(q, d_m2n, rstream); });
 }
 
 }  // namespace spc
