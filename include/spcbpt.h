@@ -205,7 +205,9 @@ typedef struct spcbpt_ctx spcbpt_ctx;
 /* Replaces LoadScene + LightSource_shift + Scene_shift + sutil::Scene::finalize
  * (optixPathTracer.cpp:729-741; sutil/Scene.cpp:731-739: context, GAS, IAS,
  * modules, program groups, pipeline, SBT).  Uploads the scene and builds the
- * software LBVH.  device = HIP device ordinal. */
+ * software LBVH.  device = HIP device ordinal.  The geometry is checked first, before a device is asked for:
+ * SPCBPT_ERR_INVALID_ARG (text: spcbpt_last_error(NULL), naming the first offender) for a vertex coordinate, light corner
+ * or light edge that is NaN or infinite and for a vertex index >= n_vertices; spcbpt_create_lit does the same. */
 int spcbpt_create(const spcbpt_scene_desc* scene, int device, spcbpt_ctx** out);
 
 /* Mesh lights: emissive meshes as area lights.  The reference routes every mesh whose material has |emissive_factor| > 0 to its

@@ -24,16 +24,37 @@ static int create_context(const spcbpt_scene_desc* sc, const spcbpt_mesh_light* 
             return SPCBPT_ERR_INVALID_ARG;
         }
     }
+    // validate the geometry before anything reaches the builder or a kernel -- and before a device is asked for: a scene that cannot be
+    // built is refused the same way with and without one.  The builder's std::min / std::max drop a NaN silently, and an infinite corner
+    // leaves no finite box to quantise: non-finite coordinates (every route ends here: .scene and glTF files are loaded into a scene desc) go back.
+    for (int v = 0; v < sc->n_vertices; v++)
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(sc->vertices[3 * (size_t)v + k])) {
+                g_create_error = "vertex " + std::to_string(v) + " has a non-finite coordinate (" + "xyz"[k] + ")";
+                return SPCBPT_ERR_INVALID_ARG;
+            }
+    for (int i = 0; i < sc->n_lights; i++)
+        for (int k = 0; k < 3; k++) {
+            const spcbpt_quad_light& s = sc->lights[i];
+            const float corner_u = s.position[k] + s.u[k], corner_v = s.position[k] + s.v[k];   // the corners the emitter triangles get below
+            if (!std::isfinite(s.position[k]) || !std::isfinite(s.u[k]) || !std::isfinite(s.v[k]) || !std::isfinite(corner_u) || !std::isfinite(corner_v) ||
+                !std::isfinite(corner_u + corner_v - s.position[k])) {
+                g_create_error = "quad light " + std::to_string(i) + " has a non-finite corner or edge (" + "xyz"[k] + ")";
+                return SPCBPT_ERR_INVALID_ARG;
+            }
+        }
+    for (int t = 0; t < sc->n_triangles; t++) {
+        for (int k = 0; k < 3; k++)
+            if (sc->indices[3 * (size_t)t + k] >= (uint32_t)sc->n_vertices) {
+                g_create_error = "vertex index out of range (triangle " + std::to_string(t) + ": index " + std::to_string(sc->indices[3 * (size_t)t + k]) + " of " + std::to_string(sc->n_vertices) + " vertices)";
+                return SPCBPT_ERR_INVALID_ARG;
+            }
+        if (sc->tri_material[t] < 0 || sc->tri_material[t] >= sc->n_materials) { g_create_error = "material index out of range"; return SPCBPT_ERR_INVALID_ARG; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available (the MI355X path has no CPU fallback)"; return SPCBPT_ERR_NO_DEVICE; }
     if (device < 0 || device >= ndev) { g_create_error = "device ordinal out of range"; return SPCBPT_ERR_NO_DEVICE; }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return SPCBPT_ERR_NO_DEVICE; }
-    // validate indices before anything reaches a kernel
-    for (int t = 0; t < sc->n_triangles; t++) {
-        for (int k = 0; k < 3; k++)
-            if (sc->indices[3 * (size_t)t + k] >= (uint32_t)sc->n_vertices) { g_create_error = "vertex index out of range"; return SPCBPT_ERR_INVALID_ARG; }
-        if (sc->tri_material[t] < 0 || sc->tri_material[t] >= sc->n_materials) { g_create_error = "material index out of range"; return SPCBPT_ERR_INVALID_ARG; }
-    }
     int patches = 0;
     for (int i = 0; i < sc->n_lights; i++) {
         if (sc->lights[i].div_level < 1) { g_create_error = "light div_level must be >= 1"; return SPCBPT_ERR_INVALID_ARG; }

@@ -23,6 +23,22 @@ static inline uint64_t expand21(uint64_t v) {  // spread the low 21 bits to ever
     return v;
 }
 
+// A triangle without area -- two equal corners, three collinear ones: |e1 x e2| = 0, taken in double from the float corners, where
+// every product of two edge components is exact -- is never a hit.  The device's Moller-Trumbore guards with det == 0 only, and its
+// FP32 determinant of such a triangle is rounding noise (the contracted cross product is not exactly perpendicular to its factors), so a
+// ray along the line of the corners was answered with u = v = 0 and a t of that noise.  The builder gives the record of such a
+// triangle P0 for all three corners: both edges are exactly zero, the determinant is exactly zero, every entry point misses it; it keeps
+// its place in the tree (tri_orig stays a permutation) with the point P0 as its box.
+static bool zero_area(const float* a, const float* b, const float* c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)   // (this function only: a product fused into the difference would not be the product)
+#endif
+    const double e1[3] = {(double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2]}, e2[3] = {(double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2]};
+    const double xy = e1[1] * e2[2], yx = e1[2] * e2[1], yz = e1[2] * e2[0], zy = e1[0] * e2[2], zx = e1[0] * e2[1], xz = e1[1] * e2[0];
+    const double n[3] = {xy - yx, yz - zy, zx - xz};
+    return n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0;
+}
+
 struct Builder {
     const HostMesh& m;
     int n;
@@ -355,8 +371,9 @@ struct Builder {
             const uint32_t* ix = m.indices + 3 * (size_t)t;
             float* q = &out.tris[(size_t)16 * i];
             float uv[3][2];
+            const bool flat = zero_area(P + 3 * (size_t)ix[0], P + 3 * (size_t)ix[1], P + 3 * (size_t)ix[2]);
             for (int v = 0; v < 3; v++) {
-                const float* p = P + 3 * (size_t)ix[v];
+                const float* p = P + 3 * (size_t)ix[flat ? 0 : v];
                 q[4 * v + 0] = p[0]; q[4 * v + 1] = p[1]; q[4 * v + 2] = p[2];
                 uv[v][0] = m.texcoords ? m.texcoords[2 * (size_t)ix[v]] : 0.0f;
                 uv[v][1] = m.texcoords ? m.texcoords[2 * (size_t)ix[v] + 1] : 0.0f;

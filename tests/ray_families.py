@@ -81,7 +81,8 @@ def family(name, scene_name, P, lo, hi, n=N):
     if name == "shadow":
         e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
         nh = np.cross(e1, e2)
-        nh = nh / np.linalg.norm(nh, axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):   # (a zero-area triangle has no normal: its pairs fail the |n^.d^| test below)
+            nh = nh / np.linalg.norm(nh, axis=1, keepdims=True)
         os_, ds_, ls_ = [], [], []
         have = 0
         for _ in range(64):

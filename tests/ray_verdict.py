@@ -19,6 +19,10 @@ Closest-hit answer (tri, t_dev): tri == -1 is accepted iff no clear hit exists; 
 accepted iff some possible hit exists (no culling), 1 (visible) iff no clear hit exists.
 A ray is AMBIGUOUS when more than one answer is acceptable -- a property of ray and verdict, never of the device.  A ray with a
 possible hit at |cos| <= 1e-4 (a coplanar ray) has no defined answer: it is reported as ambiguous and is never counted as passed.
+A ZERO-AREA triangle (|e1 x e2| = 0 in float64: two equal corners, three collinear ones) is never a hit: neither clear nor possible nor
+coplanar, set explicitly and not left to NaN compares; an answer that names one is unexplained.  Bit-identical copies of one triangle
+are ONE answer: they count once among the acceptable answers of a ray, and the "second-nearest clear hit" is the nearest of OTHER
+geometry (a scene without copies sees no difference).
 
 K and KT start at 64 and 16: tests/test_ray_verdict_cpu.py holds these constants to the CPU oracle (zero unexplained answers) and to
 seeded corruptions of its answers (all flagged).
@@ -75,6 +79,10 @@ class Verdict:
             ed = np.stack([P1 - P0, P2 - P1, P0 - P2], 1)
             ed = ed / np.linalg.norm(ed, axis=2)[..., None]
             self.edge_m = np.cross(self.nhat[:, None, :], ed)
+        self.degenerate = ~(nl > 0.0)
+        first = {}
+        self.group = np.array([first.setdefault(tri.tobytes(), i) for i, tri in enumerate(self.P)], dtype=np.int64)   # first bit-identical copy
+        self._copies = bool((self.group != np.arange(self.T)).any())
         self.P0 = P0
         self._nP0 = (self.nhat * P0).sum(1)
         self._mA = (self.edge_m * self.edge_a).sum(2)
@@ -90,6 +98,7 @@ class Verdict:
             s = np.asarray(sel, dtype=np.int64)
             pick = lambda a: a[s][:, None]
         nhat, P0, sinphi, A, M, culled = pick(self.nhat), pick(self.P0), pick(self.sinphi), pick(self.edge_a), pick(self.edge_m), pick(self.culled)
+        degenerate = pick(self.degenerate)
         with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
             dl = np.linalg.norm(d, axis=2)                     # (B, 1)
             if sel is None:
@@ -119,7 +128,7 @@ class Verdict:
             ac = np.abs(cos)
             acm = np.maximum(ac, COS_MIN)
             tt = np.maximum(T_REL * np.maximum(1.0, np.abs(t)), self.kt * EPS * (oP0 + self.ext) / (sinphi * acm * dl))
-        return dict(t=t, cos=cos, ac=ac, acm=acm, dist=dist, dw=dw, dw0=dw0, tt=tt, h=h, culled=culled)
+        return dict(t=t, cos=cos, ac=ac, acm=acm, dist=dist, dw=dw, dw0=dw0, tt=tt, h=h, culled=culled, degenerate=degenerate)
 
     @staticmethod
     def _flags(q, tmin, tmax, cull):
@@ -136,6 +145,8 @@ class Verdict:
             if cull:
                 clear &= ~q["culled"] | (cos < -COS_MIN)
                 possible &= ~q["culled"] | (cos < COS_MIN)
+            solid = ~q["degenerate"]   # a zero-area triangle is never a hit
+            clear, possible, coplanar = clear & solid, possible & solid, coplanar & solid
         return clear, possible, coplanar
 
     def _summary(self, q, tmin, tmax, cull):
@@ -146,13 +157,22 @@ class Verdict:
         i1 = tc.argmin(1)
         t1 = tc[rows, i1]
         has = np.isfinite(t1)
-        tc[rows, i1] = np.inf
+        if self._copies:
+            tc[self.group[None, :] == self.group[i1][:, None]] = np.inf   # the nearest and its bit-identical copies
+        else:
+            tc[rows, i1] = np.inf
         i2 = tc.argmin(1)
         t2 = tc[rows, i2]
         lim = np.where(has, t1 + T_REL * np.maximum(1.0, np.abs(t1)), np.inf)
         with np.errstate(invalid="ignore"):
             acc = possible & (q["t"] <= lim[:, None])
-        n_acc = acc.sum(1) + (~has)
+        if self._copies:   # copies of one triangle are one answer
+            ug, inv = np.unique(self.group, return_inverse=True)
+            onehot = np.zeros((self.T, len(ug)), dtype=np.float32)
+            onehot[np.arange(self.T), inv] = 1.0
+            n_acc = ((acc.astype(np.float32) @ onehot) > 0).sum(1) + (~has)
+        else:
+            n_acc = acc.sum(1) + (~has)
         with np.errstate(invalid="ignore", divide="ignore"):
             margin = np.where(has, (q["dist"] * q["ac"] / q["dw"])[rows, i1], np.inf)
         cop = coplanar.any(1)

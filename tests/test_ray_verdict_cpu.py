@@ -74,7 +74,8 @@ def _adjacent(P):
     return [set().union(*(key[v.tobytes()] for v in tri)) for tri in P]
 
 
-def test_seeded_corruptions_are_flagged(sc):
+def seeded_corruptions(sc):
+    """(touched, flagged) per kind of corruption: the unambiguous rays each one changes, and how many of those the verdict then rejects"""
     V = sc["verdict"]
     rng = np.random.default_rng(99)
     adj = _adjacent(V.P)
@@ -116,6 +117,11 @@ def test_seeded_corruptions_are_flagged(sc):
         assert V.judge_any(tab, a["vis"])["ok"][m].all()
         j = V.judge_any(tab, 1 - a["vis"])
         touched["visibility"] += int(m.sum()); flagged["visibility"] += int((~j["ok"])[m].sum())
+    return touched, flagged
+
+
+def test_seeded_corruptions_are_flagged(sc):
+    touched, flagged = seeded_corruptions(sc)
     for k in touched:
         print(sc["name"], k, flagged[k], "/", touched[k])
         assert touched[k] >= 500 and flagged[k] >= 0.99 * touched[k], (sc["name"], k, flagged[k], touched[k])

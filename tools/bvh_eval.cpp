@@ -4,7 +4,7 @@
 //   closest-hit rays  from area-weighted surface points along cosine-weighted directions (what path segments look like), and
 //   shadow rays       between pairs of area-weighted surface points (what connections look like),
 // and prints node visits and triangle tests per ray.  mesh file: int32 nv, nt; float32 vertices[nv][3]; uint32 indices[nt][3]
-//   g++ -O2 -std=c++17 -o /tmp/bvh_eval tools/bvh_eval.cpp && /tmp/bvh_eval mesh.bin [rays]
+//   g++ -O2 -std=c++17 -ffp-contract=off -o /tmp/bvh_eval tools/bvh_eval.cpp && /tmp/bvh_eval mesh.bin [rays [ray file]]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../spcbpt-optix7_amd/csrc/lbvh.cpp"
+#include "slab_host.h"
 
 using namespace spc;
 
@@ -27,6 +28,7 @@ static V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b
 static V3 norm(V3 a) { float l = std::sqrt(dot(a, a)); return a * (1.0f / l); }
 
 static uint64_t g_depth_ray[64], g_depth_step[64];   // stack depth: per ray its maximum, per step (node visit) the entries held -- what an N-entry LDS stack would have to spill
+static int g_deepest = 0;   // the largest number of stack entries any ray held
 static std::vector<uint64_t> g_visits;   // per node: how often it was visited (top-of-tree share, printed at the end)
 struct Stats { double nodes = 0, tris = 0, leaves = 0, rays = 0, hits = 0, leaves_exact = 0, tris_exact = 0, tri_steps = 0; };   // tri_steps: triangle steps of a lane when a fan pair is one step (Lbvh::pairs)   // *_exact: leaf visits / tests left if the leaf's child box were the exact bounds of its triangles
 
@@ -52,11 +54,12 @@ static bool traverse(const Lbvh& B, V3 o, V3 d, float tmin, float tmax, bool any
     uint32_t cur = 0;   // node index, or leaf ref with bit 31
     float best = tmax;
     bool hit = false;
-    const float inv[3] = {1.0f / (std::fabs(d.x) > 1e-20f ? d.x : 1e-20f), 1.0f / (std::fabs(d.y) > 1e-20f ? d.y : 1e-20f), 1.0f / (std::fabs(d.z) > 1e-20f ? d.z : 1e-20f)};
+    const float inv[3] = {slab_host::slab_inv(d.x), slab_host::slab_inv(d.y), slab_host::slab_inv(d.z)};
     const float oo[3] = {o.x, o.y, o.z};
+    const slab_host::Ray sr(oo, inv);   // the child boxes are tested with the device's own expression (slab_host.h)
     st.rays++;
     int sp_max = 0;
-    struct DepthNote { int& m; ~DepthNote() { g_depth_ray[std::min(m, 63)]++; } } note{sp_max};
+    struct DepthNote { int& m; ~DepthNote() { g_depth_ray[std::min(m, 63)]++; g_deepest = std::max(g_deepest, m); } } note{sp_max};
     while (true) {
         sp_max = std::max(sp_max, sp);
         if (cur & 0x80000000u) {
@@ -90,22 +93,12 @@ static bool traverse(const Lbvh& B, V3 o, V3 d, float tmin, float tmax, bool any
         if (!g_visits.empty()) g_visits[cur]++;
         uint32_t w[16];
         memcpy(w, &B.nodes[(size_t)cur * 16], sizeof(w));
-        float org[3]; memcpy(org, w, 12);
-        float sc[3];
-        for (int k = 0; k < 3; k++) { const uint32_t e = ((w[3] >> (8 * k)) & 0xffu) << 23; memcpy(&sc[k], &e, 4); }
-        const uint32_t qlo[3] = {w[4], w[5], w[6]}, qhi[3] = {w[7], w[8], w[9]};
         const uint32_t refs[4] = {w[10], w[11], w[12], w[13]};
         float key[4]; uint32_t rf[4]; int n = 0;
         for (int i = 0; i < 4; i++) {
             if (refs[i] == 0x80000000u) continue;
-            float t0 = tmin, t1 = best;
-            for (int k = 0; k < 3; k++) {
-                const float lo = org[k] + (float)((qlo[k] >> (8 * i)) & 0xffu) * sc[k], hi = org[k] + (float)((qhi[k] >> (8 * i)) & 0xffu) * sc[k];
-                float a = (lo - oo[k]) * inv[k], b = (hi - oo[k]) * inv[k];
-                if (a > b) std::swap(a, b);
-                t0 = std::max(t0, a); t1 = std::min(t1, b);
-            }
-            if (t0 <= t1 * 1.0000004f) { key[n] = t0; rf[n] = refs[i]; n++; }
+            float t0;
+            if (slab_host::slot_hit(w, i, sr, tmin, best, &t0)) { key[n] = t0; rf[n] = refs[i]; n++; }
         }
         for (int i = 1; i < n; i++) for (int j = i; j > 0 && key[j] < key[j - 1]; j--) { std::swap(key[j], key[j - 1]); std::swap(rf[j], rf[j - 1]); }
         if (n == 0) { if (sp == 0) break; cur = stack[--sp]; continue; }
@@ -271,7 +264,7 @@ static bool otraverse(const std::vector<ONode>& T, const Lbvh& B, V3 o, V3 d, fl
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: bvh_eval mesh.bin [rays]\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: bvh_eval mesh.bin [rays [ray file]]\n"); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     int hdr[2];
@@ -323,6 +316,22 @@ int main(int argc, char** argv) {
         V3 dv = Q - P;
         const float len = std::sqrt(dot(dv, dv));
         if (len > 1e-4f) traverse(B, P, dv * (1.0f / len), 1e-3f, len - 1e-3f, true, ss);
+    }
+    if (argc > 3) {   // rays of the caller's: float32 [o, tmin, d, tmax] each, traced as closest-hit and as any-hit rays; the deepest stack among them
+        FILE* rf = fopen(argv[3], "rb");
+        if (!rf) return 2;
+        const int before = g_deepest;
+        g_deepest = 0;
+        Stats sf;
+        float r[8];
+        long long n_file = 0;
+        while (fread(r, 4, 8, rf) == 8) {
+            n_file++;
+            for (int any = 0; any < 2; any++) traverse(B, V3{r[0], r[1], r[2]}, V3{r[4], r[5], r[6]}, r[3], r[7], any != 0, sf);
+        }
+        fclose(rf);
+        printf("rays of %s: %lld, hit rate %.3f, deepest stack of a ray: %d entries (3 x depth = %d)\n", argv[3], n_file, sf.hits / std::max(1.0, sf.rays), g_deepest, 3 * B.depth);
+        g_deepest = std::max(g_deepest, before);
     }
     printf("nodes %zu  depth %d  build %.2f s\n", B.nodes.size() / 16, B.depth, build_s);
     printf("steps per ray (node visits + triangle steps, a fan pair = one step): closest %.2f  shadow %.2f\n", (sc.nodes + sc.tri_steps) / sc.rays, (ss.nodes + ss.tri_steps) / ss.rays);
@@ -428,6 +437,7 @@ int main(int argc, char** argv) {
     {   // traversal-stack depth (entries held): cumulative share of the rays whose maximum / of the node visits made at depth <= N
         double rays = 0, steps = 0;
         for (int i = 0; i < 64; i++) { rays += (double)g_depth_ray[i]; steps += (double)g_depth_step[i]; }
+        printf("deepest stack of a ray: %d entries (3 x depth = %d)\n", g_deepest, 3 * B.depth);
         printf("stack depth <= N: rays (their maximum) / node visits:");
         double cr = 0, cs = 0;
         for (int i = 0; i < 64; i++) {
