@@ -549,6 +549,65 @@ int spcbpt_denoise_host(const float* accum_rgba, const float* albedo_rgba, const
                         const float eye[3], const float U[3], const float V[3], const float W[3],
                         int width, int height, const spcbpt_denoise_params* params, float* out_rgba);
 
+/* Reflected guides (no reference counterpart), opt-in: a second pair of guide planes in the layout of the first-hit feature buffers,
+ * for which the primary ray is followed through mirror-like surfaces to the first surface that is not one.  A smooth metal shows its
+ * own albedo, normal and depth in the first-hit planes, so a denoiser guided by them filters what the mirror reflects as if it were
+ * irradiance on one flat surface; guided by these planes it sees the edges of the reflected scene.
+ * Per pixel-sample (the ray of spcbpt_launch_features: camera_ray with the film's seed and subframe, from the centre of the lens),
+ * with throughput (1, 1, 1), length 0 and the segments traced over (SPCBPT_SCENE_EPSILON, 1e16) like path rays:
+ *   miss of the primary ray    albedo (1, 1, 1), coverage 0, normal 0, depth 0                  (the first-hit planes' miss)
+ *   emitter, front side        albedo = throughput, coverage 1, the light's normal unfolded, depth = length + t
+ *   emitter, back side         as a miss of that segment
+ *   followed surface           a surface with roughness <= roughness_max && metallic >= metallic_min (false for a NaN), while fewer
+ *                              than max_bounces mirrors have been followed:  throughput *= tint,  length += t,  on from the hit point
+ *                              along R = dir - 2 (N.dir) N,  N the geometric normal turned against the ray;
+ *                              tint = lerp(Cspec0, 1, schlick(|N.dir|)): the specular Fresnel colour of the BSDF at H = N
+ *   any other surface          albedo = throughput x base colour (textured as in the first-hit planes), coverage 1, N unfolded,
+ *                              depth = length + t
+ *   miss of a later segment    the last mirror shows sky or void: albedo = throughput (that mirror's tint included), coverage 1, that
+ *                              mirror's N unfolded through the mirrors before it, depth = the length up to that mirror
+ * Unfolding carries a normal n found behind a mirror of normal N back through it, n - 2 (n.N) N, through all mirrors of the chain in
+ * reverse order; depth is the unfolded path length.  The denoiser's position is eye + depth x primary direction: behind a planar
+ * mirror that is the position of the virtual image, and the unfolded normal lives in the same space.  Curved mirrors work
+ * approximately.  max_bounces = 0, or a roughness_max below every material's roughness, gives the first-hit planes bit for bit.
+ * The three parameters are dials, not tuned against any image: the defaults follow up to 4 mirrors of roughness <= 0.1 and
+ * metallic >= 0.9; a glossy dielectric (metallic 0) is mostly diffuse and stays with its own albedo. */
+typedef struct spcbpt_guide_params {
+    int32_t max_bounces;              /* 0 .. 8 */
+    float roughness_max, metallic_min;
+} spcbpt_guide_params;
+#define SPCBPT_GUIDE_MAX_BOUNCES 4
+#define SPCBPT_GUIDE_ROUGHNESS_MAX 0.1f
+#define SPCBPT_GUIDE_METALLIC_MIN 0.9f
+int spcbpt_guide_params_struct_size(void);   /* sizeof(spcbpt_guide_params) as the library was compiled */
+/* One subframe's samples into the running means of the two guide planes (lerp(prev, sample, 1 / (subframe + 1)); subframe 0
+ * overwrites), rows as in spcbpt_launch_features (8-row bands; rows outside them are left alone).  The planes are allocated (zeroed)
+ * at the first guide launch after spcbpt_resize, which frees them.  SPCBPT_ERR_INVALID_ARG for NULL params, max_bounces outside
+ * 0 .. 8, a NaN parameter or a row_begin that is not a multiple of 8; SPCBPT_ERR_STATE before spcbpt_resize, before a camera is set
+ * and while a deferred frame is outstanding.  Asynchronous, a link of the film-merge chain like spcbpt_launch_features; no other
+ * plane is touched, event counters are not charged, the kernel-time span is "guides". */
+int spcbpt_launch_guides(spcbpt_ctx* ctx, uint32_t subframe, int row_begin, int row_end, int row_step, const spcbpt_guide_params* params);
+/* Host copies of the two planes (either may be NULL); waits like spcbpt_read_accum.  SPCBPT_ERR_STATE if no guide launch has been
+ * made since the last spcbpt_resize. */
+int spcbpt_read_guides(spcbpt_ctx* ctx, float* albedo_rgba, float* normal_depth_rgba);
+/* Which pair of planes spcbpt_denoise and spcbpt_denoise_variance take albedo and normal + depth from.  SPCBPT_GUIDES_FIRST_HIT (the
+ * default): every call gives the bits it gave without this switch.  SPCBPT_GUIDES_REFLECTED: the guide planes; both denoisers then
+ * refuse with SPCBPT_ERR_STATE (the text names spcbpt_launch_guides) if no guide launch has been made since the last spcbpt_resize.
+ * Any other value: SPCBPT_ERR_INVALID_ARG.  The switch outlives spcbpt_resize.  spcbpt_history_capture / _reproject / _resolve /
+ * _denoise and the adaptive calls keep the first-hit planes whatever it says: reprojection is the geometry of the first hit. */
+#define SPCBPT_GUIDES_FIRST_HIT 0
+#define SPCBPT_GUIDES_REFLECTED 1
+int spcbpt_set_denoise_guides(spcbpt_ctx* ctx, int which);
+/* The per-bounce arithmetic of the guide pass over host arrays, the functions the kernel runs (float32, no contraction; no context
+ * and no GPU needed).  n records: dir and normal 3 floats each (the ray direction; the hit's unit normal turned against the ray),
+ * material 6 floats (base r, g, b, metallic, roughness, specular) and specular_tint 1 float, test_normal 3 floats (a normal found
+ * behind the mirror).  Out, each optional: followed (1 / 0: the roughness / metallic rule of `params`; max_bounces is not looked
+ * at), reflected (R), tint and unfolded (the test normal carried back through the mirror), 3 floats per record.
+ * SPCBPT_ERR_INVALID_ARG for a NULL input or n < 1. */
+int spcbpt_guide_step_host(int64_t n, const float* dir, const float* normal, const float* material, const float* specular_tint,
+                           const float* test_normal, const spcbpt_guide_params* params,
+                           int32_t* followed, float* reflected, float* tint, float* unfolded);
+
 /* Second moment of the film (no reference counterpart), opt-in: spcbpt_set_film_moments(ctx, 1).  Off (the default) a context keeps
  * its footprint, its launches and its film bits.  On, the context keeps one float4-per-pixel plane in the film's row order,
  *   m2n(p) = (M2_r, M2_g, M2_b, n),

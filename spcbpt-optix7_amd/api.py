@@ -60,6 +60,14 @@ class DenoiseParams(C.Structure):   # spcbpt_denoise_params
     _fields_ = [("iterations", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_x", C.c_float)]
 
 
+class GuideParams(C.Structure):   # spcbpt_guide_params
+    _fields_ = [("max_bounces", C.c_int32), ("roughness_max", C.c_float), ("metallic_min", C.c_float)]
+
+
+GUIDE_MAX_BOUNCES, GUIDE_ROUGHNESS_MAX, GUIDE_METALLIC_MIN = 4, 0.1, 0.9   # SPCBPT_GUIDE_*: dials, not tuned against any image
+DENOISE_GUIDES = {"first_hit": 0, "reflected": 1}                          # SPCBPT_GUIDES_*
+
+
 class ReprojectParams(C.Structure):   # spcbpt_reproject_params
     _fields_ = [("sigma_n", C.c_float), ("sigma_x", C.c_float), ("max_history", C.c_float)]
 
@@ -442,6 +450,25 @@ def denoise_host(accum, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_
     if rc != 0:
         raise SpcbptError(f"denoise_host failed ({rc})")
     return out
+
+
+def guide_step_host(dir, normal, material, specular_tint, test_normal, roughness_max=GUIDE_ROUGHNESS_MAX, metallic_min=GUIDE_METALLIC_MIN):
+    """spcbpt_guide_step_host: the per-bounce arithmetic of Renderer.launch_guides over n records -- dir, normal and test_normal (n, 3),
+    material (n, 6): base r, g, b, metallic, roughness, specular; specular_tint (n,).  Returns (followed (n,) bool, reflected (n, 3), tint
+    (n, 3), unfolded (n, 3)): the roughness / metallic rule, R = dir - 2 (N.dir) N, the mirror's Fresnel colour, and test_normal carried
+    back through the mirror.  Host code in float32 -- the functions the kernel runs; no GPU needed."""
+    lib = load_library()
+    d, N, m, st, tn = (np.ascontiguousarray(x, dtype=np.float32) for x in (dir, normal, material, specular_tint, test_normal))
+    n = len(st)
+    if n < 1 or d.shape != (n, 3) or N.shape != (n, 3) or tn.shape != (n, 3) or m.shape != (n, 6) or st.shape != (n,):
+        raise SpcbptError("guide_step_host: dir, normal and test_normal must be (n, 3), material (n, 6), specular_tint (n,)")
+    p = GuideParams(0, float(roughness_max), float(metallic_min))
+    followed = np.zeros(n, np.int32)
+    R, tint, unf = (np.zeros((n, 3), np.float32) for _ in range(3))
+    rc = lib.spcbpt_guide_step_host(n, _fp(d), _fp(N), _fp(m), _fp(st), _fp(tn), C.byref(p), followed.ctypes.data_as(C.POINTER(C.c_int32)), _fp(R), _fp(tint), _fp(unf))
+    if rc != 0:
+        raise SpcbptError(f"guide_step_host failed ({rc})")
+    return followed != 0, R, tint, unf
 
 
 def denoise_variance_host(accum, m2n, albedo, normal_depth, eye, U, V, W, iterations=5, sigma_v=0.0, sigma_n=0.0, sigma_x=0.0):
@@ -1090,6 +1117,11 @@ def load_library(path: str = LIB_PATH):
         "spcbpt_splat_sum_host": [f32p, C.POINTER(C.c_int32), C.c_int64, i32, i32, f32p],
         "spcbpt_launch_features": [vp, u32, i32, i32, i32],
         "spcbpt_read_features": [vp, vp, vp],
+        "spcbpt_launch_guides": [vp, u32, i32, i32, i32, C.POINTER(GuideParams)],
+        "spcbpt_read_guides": [vp, vp, vp],
+        "spcbpt_set_denoise_guides": [vp, i32],
+        "spcbpt_guide_params_struct_size": [],
+        "spcbpt_guide_step_host": [C.c_int64, f32p, f32p, f32p, f32p, f32p, C.POINTER(GuideParams), C.POINTER(C.c_int32), f32p, f32p, f32p],
         "spcbpt_denoise": [vp, C.POINTER(DenoiseParams)],
         "spcbpt_denoise_params_struct_size": [],
         "spcbpt_read_denoised": [vp, vp, vp],
@@ -1211,6 +1243,7 @@ EXPORTED_SYMBOLS = [
     "spcbpt_set_splat_order", "spcbpt_get_splat_order", "spcbpt_read_splat_records", "spcbpt_splat_sum_host",
     "spcbpt_set_lens", "spcbpt_get_lens", "spcbpt_camera_lens_ray_host", "spcbpt_camera_splat_lens", "spcbpt_lens_sample_host", "spcbpt_debug_lens_rays",
     "spcbpt_launch_features", "spcbpt_read_features", "spcbpt_denoise", "spcbpt_denoise_params_struct_size", "spcbpt_read_denoised", "spcbpt_denoise_host",
+    "spcbpt_launch_guides", "spcbpt_read_guides", "spcbpt_set_denoise_guides", "spcbpt_guide_params_struct_size", "spcbpt_guide_step_host",
     "spcbpt_set_film_moments", "spcbpt_get_film_moments", "spcbpt_read_film_moments", "spcbpt_film_moments_update_host", "spcbpt_film_error", "spcbpt_film_error_struct_size", "spcbpt_film_error_host", "spcbpt_denoise_variance", "spcbpt_denoise_variance_host",
     "spcbpt_set_film_buckets", "spcbpt_get_film_buckets", "spcbpt_read_film_buckets", "spcbpt_film_buckets_update_host", "spcbpt_robust_resolve", "spcbpt_read_robust", "spcbpt_robust_resolve_host",
     "spcbpt_display_default_params", "spcbpt_display_params_struct_size", "spcbpt_display", "spcbpt_display_image", "spcbpt_read_display", "spcbpt_display_reset", "spcbpt_display_host",
@@ -1385,6 +1418,19 @@ class Renderer:
         merged into the feature buffers as a running mean over the subframes; rows as in launch()."""
         r0, r1, rs = rows if rows is not None else (0, self.height, 1)
         self._chk(self.lib.spcbpt_launch_features(self.h, int(subframe), r0, r1, rs), "launch_features")
+
+    def launch_guides(self, subframe: int, rows=None, max_bounces=GUIDE_MAX_BOUNCES, roughness_max=GUIDE_ROUGHNESS_MAX, metallic_min=GUIDE_METALLIC_MIN):
+        """spcbpt_launch_guides: launch_features' ray followed through up to `max_bounces` (0 .. 8) mirror-like surfaces (roughness <=
+        roughness_max and metallic >= metallic_min) to the first surface that is not one; albedo x the mirrors' tints + coverage, and
+        the normal + path length unfolded through the mirrors, merged into the guide planes as running means; rows as in launch()."""
+        r0, r1, rs = rows if rows is not None else (0, self.height, 1)
+        p = GuideParams(int(max_bounces), float(roughness_max), float(metallic_min))
+        self._chk(self.lib.spcbpt_launch_guides(self.h, int(subframe), r0, r1, rs, C.byref(p)), "launch_guides")
+
+    def set_denoise_guides(self, which):
+        """spcbpt_set_denoise_guides: "first_hit" (the default) or "reflected" -- the planes denoise() and denoise_variance() take albedo
+        and normal + depth from (launch_guides first for "reflected").  The history calls and adaptive sampling keep the first hit."""
+        self._chk(self.lib.spcbpt_set_denoise_guides(self.h, DENOISE_GUIDES[which] if isinstance(which, str) else int(which)), "set_denoise_guides")
 
     def denoise(self, iterations=5, sigma_c=0.0, sigma_n=0.0, sigma_x=0.0):
         """spcbpt_denoise: the edge-avoiding a-trous filter on the film divided by the first-hit albedo, guided by the feature buffers
@@ -1680,6 +1726,14 @@ class Renderer:
         a = np.zeros((self.height, self.width, 4), dtype=np.float32)
         n = np.zeros((self.height, self.width, 4), dtype=np.float32)
         self._chk(self.lib.spcbpt_read_features(self.h, a.ctypes.data, n.ctypes.data), "read_features")
+        return a, n
+
+    def read_guides(self):
+        """(albedo, normal_depth): (h, w, 4) float32 each -- the reflected guide planes in read_features' layout (spcbpt_read_guides)."""
+        self.image_size()
+        a = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        n = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._chk(self.lib.spcbpt_read_guides(self.h, a.ctypes.data, n.ctypes.data), "read_guides")
         return a, n
 
     def read_film_moments(self):

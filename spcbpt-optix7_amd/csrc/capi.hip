@@ -389,6 +389,7 @@ int spcbpt_resize(spcbpt_ctx* c, int w, int h) {
     c->adaptive_drop();           // adaptive sampling ends with the film its tiles belong to
     c->d_accum.release(); c->d_frame.release();
     c->free_features();           // feature buffers and denoiser planes of the old size: re-allocated on demand
+    c->free_guides();             // ... and the reflected guide planes
     c->free_moments();            // ... and the film's second moment
     c->free_buckets();            // ... and the bucket film with its resolved image (K stays)
     c->free_display();            // ... and the display plane with its record: the previous EV is forgotten

@@ -4,6 +4,7 @@
 //   ctx_exchange.hip  Context: the shards and imports of a sharded job (what libspcbpt_mgpu drives)
 //   ctx_render.hip    Context: eye / pt launches (single, deferred, batched), film merges
 //   ctx_features.hip  Context + extern "C": the first-hit feature pass, the a-trous denoiser and the driver the three denoisers share
+//   ctx_guides.hip    Context + extern "C": the reflected-guide pass and the switch that makes the two film denoisers read its planes
 //   ctx_moments.hip   Context + extern "C": the film's second moment, the film error, the variance-guided denoiser
 //   ctx_buckets.hip   Context + extern "C": the bucket film and its median-of-means resolve
 //   ctx_display.hip   Context + extern "C": the display transform -- exposure, histogram auto-exposure, tone operators

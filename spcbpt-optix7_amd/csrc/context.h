@@ -373,8 +373,18 @@ struct Context {
     // (the caller's launch, from `input`), the a-trous passes of either form, k_remodulate --, have_denoised and the end of the link.
     int denoise_begin(const char* who, const spcbpt_denoise_params& p);
     int denoise_run(const char* who, const spcbpt_denoise_params& p, float sigma_c_default, const float* input, bool variance_guided,
-                    const std::function<void(const DenoiseParams&)>& demodulate);
+                    const std::function<void(const DenoiseParams&)>& demodulate, const float* albedo = nullptr, const float* normal_depth = nullptr);
     void free_features();
+    // Reflected guides (ctx_guides.hip; spcbpt_launch_guides): a second pair of float4 planes, the first-hit planes' layout, filled by
+    // k_guides with what the first surface that is not mirror-like shows along the primary ray's chain of reflections.  Allocated (zeroed)
+    // at the first guide launch after a resize, freed by spcbpt_resize.  denoise_guides (spcbpt_set_denoise_guides; it outlives a resize)
+    // makes spcbpt_denoise and spcbpt_denoise_variance -- and nothing else -- read them in place of the first-hit planes.
+    DevBuf<float> d_guide_albedo, d_guide_normal_depth;
+    bool have_guides = false;                                         // ... since the last resize
+    int denoise_guides = SPCBPT_GUIDES_FIRST_HIT;
+    int launch_guides(uint32_t subframe, int r0, int r1, int rs, const spcbpt_guide_params& gp);
+    int denoise_planes(const char* who, const float*& albedo, const float*& normal_depth);   // the pair the switch selects, or the refusal
+    void free_guides();
     // Second moment of the film (ctx_moments.hip; spcbpt_set_film_moments, off by default): one float4 per pixel (M2_r, M2_g, M2_b, n),
     // updated by k_film_moments in front of every film merge of finish_frame.  Allocated (zeroed) at the first merge after a resize
     // while the switch is on, freed by spcbpt_resize and by turning the switch off: a context that does not ask keeps its footprint,

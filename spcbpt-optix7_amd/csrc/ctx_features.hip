@@ -68,7 +68,7 @@ int Context::denoise_begin(const char* who, const spcbpt_denoise_params& dp) {
 // and the launches as one span `who`: the caller's demodulate of `input` -> `iterations` a-trous passes between the two planes, plain
 // or variance-guided -> remodulate + tone map.  Ends the link.
 int Context::denoise_run(const char* who, const spcbpt_denoise_params& dp, float sigma_c_default, const float* input, bool variance_guided,
-                         const std::function<void(const DenoiseParams&)>& demodulate) {
+                         const std::function<void(const DenoiseParams&)>& demodulate, const float* albedo, const float* normal_depth) {
     const float ext[3] = {bbox_hi[0] - bbox_lo[0], bbox_hi[1] - bbox_lo[1], bbox_hi[2] - bbox_lo[2]};
     const float diag = sqrtf(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]);
     const float sigma_c = dp.sigma_c > 0.0f ? dp.sigma_c : sigma_c_default;
@@ -86,7 +86,7 @@ int Context::denoise_run(const char* who, const spcbpt_denoise_params& dp, float
     memset(&q, 0, sizeof(q));
     memcpy(q.U, kp.U, 12); memcpy(q.V, kp.V, 12); memcpy(q.W, kp.W, 12);
     q.width = kp.width; q.height = kp.height;
-    q.accum = input; q.albedo = d_feat_albedo; q.normal_depth = d_feat_normal_depth;
+    q.accum = input; q.albedo = albedo ? albedo : d_feat_albedo.p; q.normal_depth = normal_depth ? normal_depth : d_feat_normal_depth.p;   // (the caller's pair: Context::denoise_planes)
     q.position = d_dn_position; q.ping = d_dn_ping; q.pong = d_dn_pong; q.denoised = d_denoised; q.frame = d_denoised_frame;
     time_begin(who, rstream);
     demodulate(q);
@@ -106,8 +106,10 @@ int Context::denoise(const spcbpt_denoise_params& dp) {
     if (deferred.active) { error = "a deferred frame is outstanding: spcbpt_merge_deferred(ctx, keep) first"; return SPCBPT_ERR_STATE; }
     if (!d_accum) { error = "denoise before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!have_features) { error = "denoise needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    const float *albedo, *normal_depth;
+    if (int rc = denoise_planes("denoise", albedo, normal_depth)) return rc;
     if (int rc = denoise_begin("denoise", dp)) return rc;
-    return denoise_run("denoise", dp, SPCBPT_DENOISE_SIGMA_C, d_accum, false, [&](const DenoiseParams& q) { launch_demodulate(q, rstream); });
+    return denoise_run("denoise", dp, SPCBPT_DENOISE_SIGMA_C, d_accum, false, [&](const DenoiseParams& q) { launch_demodulate(q, rstream); }, albedo, normal_depth);
 }
 
 }  // namespace spc

@@ -72,13 +72,15 @@ int Context::denoise_variance(const spcbpt_denoise_params& dp) {
     if (!d_accum) { error = "denoise_variance before spcbpt_resize"; return SPCBPT_ERR_STATE; }
     if (!film_moments) { error = "denoise_variance needs the film's moments: spcbpt_set_film_moments(ctx, 1) before the frames are rendered"; return SPCBPT_ERR_STATE; }
     if (!have_features) { error = "denoise_variance needs the feature buffers: spcbpt_launch_features since the last spcbpt_resize"; return SPCBPT_ERR_STATE; }
+    const float *albedo, *normal_depth;
+    if (int rc = denoise_planes("denoise_variance", albedo, normal_depth)) return rc;
     if (int rc = denoise_begin("denoise_variance", dp)) return rc;
     if (!d_m2n) {   // moments on, but no merge since the last resize: every pixel has n = 0
         const size_t px = (size_t)kp.width * kp.height;
         HIP_TRY(this, d_m2n.reserve(px * 4));
         HIP_TRY(this, hipMemsetAsync(d_m2n, 0, px * 16, rstream));
     }
-    return denoise_run("denoise_variance", dp, SPCBPT_DENOISE_SIGMA_V, d_accum, true, [&](const DenoiseParams& q) { launch_demodulate_var(q, d_m2n, rstream); });
+    return denoise_run("denoise_variance", dp, SPCBPT_DENOISE_SIGMA_V, d_accum, true, [&](const DenoiseParams& q) { launch_demodulate_var(q, d_m2n, rstream); }, albedo, normal_depth);
 }
 
 }  // namespace spc

@@ -193,6 +193,32 @@ def bedroom(target_tris: int = 1_000_000, seed: int = 0x5EED, tex_size: int = 10
     return b.finish(mats, lights, textures=texs, camera=cam, name="bedroom")
 
 
+def mirror_box(tex_size: int = 64) -> Scene:
+    """A Cornell box seen from the inside for the reflected denoiser guides (Renderer.launch_guides): the checker-textured floor of the
+    bedroom materials, a planar mirror quad on the back wall (colour (0.9, 0.8, 0.7), roughness 0.02, metallic 1), a second one on the
+    left wall that the camera sees obliquely -- some pixels see mirror -> mirror -> wall --, the ceiling light where the back mirror
+    shows it, and no right wall, so that some reflected rays leave the scene."""
+    b = _Builder()
+    FLOOR, W, R, MIRROR = 0, 1, 2, 3
+    b.grid((-1, 0, 1), (2, 0, 0), (0, 0, -2), 1, 1, FLOOR, uv_scale=2.0)   # floor (normal +y)
+    b.grid((-1, 2, -1), (2, 0, 0), (0, 0, 2), 1, 1, W)                     # ceiling
+    b.grid((-1, 0, -1), (2, 0, 0), (0, 2, 0), 1, 1, W)                     # back wall  z = -1
+    b.grid((1, 0, 1), (-2, 0, 0), (0, 2, 0), 1, 1, W)                      # front wall z = +1 (behind the camera)
+    b.grid((-1, 0, 1), (0, 0, -2), (0, 2, 0), 1, 1, R)                     # left wall  x = -1 (red); the right side is open
+    b.grid((-0.75, 0.35, -0.99), (1.5, 0, 0), (0, 1.4, 0), 1, 1, MIRROR)   # the mirror on the back wall, 1 cm in front of it
+    b.grid((-0.99, 0.4, 0.45), (0, 0, -1.25), (0, 1.2, 0), 1, 1, MIRROR)   # the mirror on the left wall
+    b.box((0.25, 0.0, -0.55), (0.65, 0.7, -0.15), W, rot_y=0.4, skip_bottom=True)   # a box whose edges the back mirror shows
+    mats = [dict(color=(0.8, 0.8, 0.8), roughness=0.6, metallic=0.0, albedo_tex=1),
+            dict(color=(0.73, 0.73, 0.73), roughness=0.5, metallic=0.0),
+            dict(color=(0.65, 0.05, 0.05), roughness=0.5, metallic=0.0),
+            dict(color=(0.9, 0.8, 0.7), roughness=0.02, metallic=1.0)]
+    # normal = normalize(cross(u, v)) = -y: emits downward, 2 mm below the ceiling, over the part of it the back mirror reflects
+    lights = [dict(position=(-0.45, 1.998, -0.7), u=(0.9, 0, 0), v=(0, 0, 0.9), emission=(17, 12, 4), div_level=10)]
+    texs = [_texture(0, tex_size, np.random.default_rng(0))]
+    cam = dict(eye=(0.2, 1.0, 0.85), lookat=(-0.25, 0.95, -1.0), up=(0, 1, 0), fov=65.0)
+    return b.finish(mats, lights, textures=texs, camera=cam, name="mirror_box")
+
+
 def hallway(target_tris: int = 200_000, seed: int = 7) -> Scene:
     """C5: hallway/door SDS scene — the light sits in an adjacent room behind a door ajar and reaches the
     camera's room only through the gap and off a glossy floor."""

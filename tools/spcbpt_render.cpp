@@ -9,6 +9,10 @@
 // --denoise: a first-hit feature launch beside every frame and one a-trous denoise (spcbpt_denoise, default parameters) after the last;
 // writes <out>_denoised.pfm / .ppm next to the usual files.  --features: writes the feature buffers as <out>_albedo.pfm,
 // <out>_normal.pfm and <out>_depth.pfm (depth in all three channels).
+// --guides [N]: with --denoise / --denoise-variance a reflected-guide launch (spcbpt_launch_guides; up to N mirrors, default
+// SPCBPT_GUIDE_MAX_BOUNCES, the other parameters at their defaults) beside the features of every frame, and the denoiser reads those planes
+// (spcbpt_set_denoise_guides); with --features also <out>_guide_albedo.pfm, <out>_guide_normal_depth.pfm (the unfolded normal) and
+// <out>_guide_depth.pfm (the unfolded path length in all three channels).  Without the flag every output file keeps its bytes.
 // --denoise-variance: the same with the variance-guided filter (spcbpt_denoise_variance; switches the film's moments on).
 // --target-error E [--check-every K]: switches the film's moments on and renders until spcbpt_film_error's mean is <= E (asked every K
 // frames, default 8, from the second frame on) or --frames is reached; prints the frames used and the error reached.
@@ -78,13 +82,14 @@ static void write_ppm(const std::string& path, const std::vector<uint8_t>& rgba8
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--batch N] [--out prefix]\n", argv[0]);
+        fprintf(stderr, "usage: %s <file.scene | file.gltf | file.glb> <data_root (ignored for glTF)> [--alg pt|SPCBPT_eye|lt] [--dim=WxH] [--frames N] [--train-paths N] [--minimal] [--env-mode N] [--emissive] [--aperture R] [--focus F] [--ordered-splat] [--denoise] [--denoise-variance] [--features] [--guides [N]] [--target-error E] [--check-every K] [--adaptive] [--min-samples M] [--max-samples X] [--robust K] [--robust-strength S] [--exposure EV] [--auto-exposure] [--tone film|reinhard|aces|linear] [--key K] [--bloom S] [--bloom-levels N] [--bloom-threshold T] [--local-tone C] [--local-detail D] [--local-cell S] [--local-range R] [--batch N] [--out prefix]\n", argv[0]);
         return 0;
     }
     std::string alg = "SPCBPT_eye", out = "render";
     int width = 1920, height = 1000, frames = 16, train_paths = 2000000;  // optixPathTracer.cpp:84-85 default size
     int env_mode = 0;
-    bool minimal = false, emissive = false, ordered_splat = false, denoise = false, features = false, denoise_variance = false;
+    bool minimal = false, emissive = false, ordered_splat = false, denoise = false, features = false, denoise_variance = false, guides = false;
+    spcbpt_guide_params gp = {SPCBPT_GUIDE_MAX_BOUNCES, SPCBPT_GUIDE_ROUGHNESS_MAX, SPCBPT_GUIDE_METALLIC_MIN};
     double target_error = 0.0;   // > 0: stop once the film's mean relative standard error is there
     int check_every = 8;
     bool adaptive = false, check_every_given = false;
@@ -115,6 +120,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-variance") denoise = denoise_variance = true;
         else if (a == "--features") features = true;
+        else if (a == "--guides") { guides = true; if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') gp.max_bounces = atoi(argv[++i]); }
         else if (a == "--target-error" && i + 1 < argc) target_error = atof(argv[++i]);
         else if (a == "--check-every" && i + 1 < argc) { check_every = atoi(argv[++i]); check_every_given = true; }
         else if (a == "--adaptive") adaptive = true;
@@ -266,6 +272,7 @@ int main(int argc, char** argv) {
             CHECK(ctx, spcbpt_launch_eye_batch_film(ctx, g, subframes, 0, height, 1));   // the samplers of the last g builds
             build_next(); light_next();
             if (denoise) for (int k = 0; k < g; k++) CHECK(ctx, spcbpt_launch_features(ctx, subframes[k], 0, height, 1));   // (--denoise-variance)
+            if (denoise && guides) for (int k = 0; k < g; k++) CHECK(ctx, spcbpt_launch_guides(ctx, subframes[k], 0, height, 1, &gp));
             f += g;
             if (!adaptive && target_error > 0.0 && f >= 2 && (f % check_every == 0 || f == frames)) {
                 CHECK(ctx, spcbpt_film_error(ctx, &reached));
@@ -282,6 +289,7 @@ int main(int argc, char** argv) {
         }
         CHECK(ctx, spcbpt_launch(ctx, alg.c_str(), (uint32_t)f, 0, height, 1));  // launchSubframe (609-635)
         if (denoise || features) CHECK(ctx, spcbpt_launch_features(ctx, (uint32_t)f, 0, height, 1));   // the same subframe's primary rays
+        if (guides && (denoise || features)) CHECK(ctx, spcbpt_launch_guides(ctx, (uint32_t)f, 0, height, 1, &gp));   // ... followed through the mirrors
         if (!adaptive && target_error > 0.0 && f >= 1 && ((f + 1) % check_every == 0 || f + 1 == frames)) {
             CHECK(ctx, spcbpt_film_error(ctx, &reached));
             if (reached.pixels > 0 && reached.mean <= target_error) { frames = f + 1; break; }
@@ -317,6 +325,7 @@ int main(int argc, char** argv) {
                (long long)reached.pixels);
     }
     if (denoise) {
+        if (guides) CHECK(ctx, spcbpt_set_denoise_guides(ctx, SPCBPT_GUIDES_REFLECTED));
         const spcbpt_denoise_params dp = {5, 0.0f, 0.0f, 0.0f};   // the defaults of include/spcbpt.h
         if (denoise_variance) CHECK(ctx, spcbpt_denoise_variance(ctx, &dp));
         else CHECK(ctx, spcbpt_denoise(ctx, &dp));
@@ -387,6 +396,13 @@ int main(int argc, char** argv) {
         write_pfm(out + "_normal.pfm", normal_depth, width, height);
         write_pfm(out + "_depth.pfm", normal_depth, width, height, 3, 3, 3);
         printf("wrote %s_albedo.pfm, %s_normal.pfm and %s_depth.pfm\n", out.c_str(), out.c_str(), out.c_str());
+        if (guides) {
+            CHECK(ctx, spcbpt_read_guides(ctx, accum.data(), normal_depth.data()));
+            write_pfm(out + "_guide_albedo.pfm", accum, width, height);
+            write_pfm(out + "_guide_normal_depth.pfm", normal_depth, width, height);
+            write_pfm(out + "_guide_depth.pfm", normal_depth, width, height, 3, 3, 3);
+            printf("wrote %s_guide_albedo.pfm, %s_guide_normal_depth.pfm and %s_guide_depth.pfm (up to %d mirrors)\n", out.c_str(), out.c_str(), out.c_str(), gp.max_bounces);
+        }
     }
     spcbpt_destroy(ctx);
     spcbpt_scene_file_free(sf);
